@@ -31,6 +31,13 @@ Extra objects on the JSON line:
                 quotes the one piece of the reference that CAN run: its own torch-CPU
                 post_physics_step (observations / rewards / resets, no physics), timed in the build
                 container (tools/time_ref_pipeline.py -> profiles/r02_ref_python_pipeline.json).
+
+--dump-outputs DIR: after the timed steps, what the last one computed -- the tensors env.step() hands its caller (observations,
+privileged observations, rewards, resets, time-outs, episode lengths) and the state the physics advanced (root states, dof
+positions / velocities) -- is written as DIR/<name>.npy (float32; int64 as float64), one row per env.  The inputs are fixed by the
+arguments (terrain seed, domain-randomisation seed, action pool seed), so two builds run with the same arguments can be compared
+output for output.  Beyond 64 MB a fixed, seeded sample of the env rows is written, the same rows for every tensor; env_index.npy
+names them.  With more than one rank every rank writes its own shard as DIR/<name>_rank<r>.npy.
 """
 import argparse
 import os
@@ -45,6 +52,8 @@ sys.path.insert(0, ROOT)
 B_FLAT, B_ROUGH = 1750.0, 2476.0   # algorithmic bytes per env-step
 HBM_PEAK_GBS = 8000.0              # MI355X HBM3E peak (MI355X_MICROARCH.md)
 VALU_ISSUE_PEAK = 256 * 4 * 2.4e9 / 2.0   # wave64 VALU instructions / s: 256 CUs x 4 SIMDs, one per 2 cycles, 2.4 GHz
+DUMP_TENSORS = ("OBS", "PRI_OBS", "REW", "RESET", "TIME_OUT", "EPISODE_LENGTH", "ROOT_STATES", "DOF_POS", "DOF_VEL")
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: all ranks together
 
 
 def cpu_model():
@@ -83,6 +92,30 @@ def make_cfg(terrain, robot="lower_limb"):
     if os.environ.get("GRX_BENCH_RBS", "0") == "1":
         cfg.env.publish_rigid_body_states = cfg.env.publish_measured_heights = "every_step"
     return cfg
+
+
+def dump_outputs(sim, out_dir, rank, world):
+    """--dump-outputs: the step's outputs as of the last launch, env rows first; a seeded sample of the rows beyond the size budget."""
+    import numpy as np
+    import torch
+    sim.wait_idle()
+    torch.cuda.synchronize()
+    arrays = {}
+    for name in DUMP_TENSORS:
+        t = sim.tensor(name)
+        assert t.shape[0] == sim.num_envs, (name, tuple(t.shape))
+        arrays[name.lower()] = t.to("cpu", torch.float64 if t.dtype in (torch.int64, torch.float64) else torch.float32)
+    n = sim.num_envs
+    row_bytes = 8 + sum(a[0].numel() * a.element_size() for a in arrays.values())   # (8: the env_index column)
+    keep = min(n, max(1, (DUMP_MAX_BYTES - (64 << 10)) // max(1, world) // row_bytes))   # (64 KB: room for the .npy headers)
+    rows = torch.arange(n) if keep == n else torch.randperm(n, generator=torch.Generator().manual_seed(12345))[:keep].sort().values
+    arrays["env_index"] = (rows + rank * n).to(torch.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        if name != "env_index":
+            a = a[rows]
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.ascontiguousarray(a.numpy()))
 
 
 def full_iteration(args, n_local, iters, warm=2):
@@ -182,6 +215,8 @@ def main():
     ap.add_argument("--train-timeout", type=float, default=150.0, help="seconds after which the full_iteration leg is given up (the line is printed without it)")
     ap.add_argument("--cpu-envs", type=int, default=4096)
     ap.add_argument("--cpu-steps", type=int, default=0, help="0 = auto (about 15 s of CPU work)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (see the module docstring)")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 2000 if args.robot == "full_body" else 20000
@@ -287,6 +322,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     finite = bool(torch.isfinite(sim.tensor("OBS")).all().item()) and bool(torch.isfinite(sim.tensor("REW")).all().item())
+    if args.dump_outputs:
+        dump_outputs(sim, args.dump_outputs, rank, world)
     out = None
     layout = sim.layout()
     if rank == 0:
