@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define GRX_ABI_VERSION 6
+#define GRX_ABI_VERSION 7
 
 #define GRX_MAX_BODIES 36   /* moving bodies after merging fixed joints (base + DOFs) */
 #define GRX_MAX_DOFS 32
@@ -110,6 +110,29 @@ typedef enum grx_reward_term {
     GRX_REW_TERMINATION,
     GRX_NUM_REWARD_TERMS
 } grx_reward_term;
+
+/* ABI 7: legged_gym's base reward terms (legged_robot.py:1277-1376) that the FFTAI / GR1 classes do not override, in ALPHABETICAL
+ * order.  A table of their own: the fused kernels size per-lane arrays and statistics rows by GRX_NUM_REWARD_TERMS.  The reference
+ * accumulates the union of both tables in alphabetical order; the library sums the 36 terms, then these (the same total up to
+ * rounding).  A handle with any of them active runs the *_base entry of its layout: one-wave lower-limb, tree or generic. */
+typedef enum grx_base_reward_term {
+    GRX_BREW_ACTION_RATE = 0,
+    GRX_BREW_ANG_VEL_XY,
+    GRX_BREW_BASE_HEIGHT,
+    GRX_BREW_DOF_ACC,
+    GRX_BREW_DOF_POS_LIMITS,
+    GRX_BREW_DOF_VEL,
+    GRX_BREW_DOF_VEL_LIMITS,
+    GRX_BREW_FEET_CONTACT_FORCES,
+    GRX_BREW_LIN_VEL_Z,
+    GRX_BREW_ORIENTATION,
+    GRX_BREW_STUMBLE,
+    GRX_BREW_TORQUE_LIMITS,
+    GRX_BREW_TORQUES,
+    GRX_BREW_TRACKING_ANG_VEL,
+    GRX_BREW_TRACKING_LIN_VEL,
+    GRX_NUM_BASE_REWARD_TERMS
+} grx_base_reward_term;
 
 /* sphere flags */
 #define GRX_SPH_FOOT_LEFT 0x1u   /* belongs to feet_indices[0] (first body whose name contains foot_name) */
@@ -293,6 +316,17 @@ typedef struct grx_config {
                                     time-based resample (legged_robot.py:320-326); the yaw command is then not drawn at resample
                                     (legged_robot.py:668-676).  commands_heading is the reference's all-zero buffer (gr1t1.py:124: it is
                                     never written; the draw of legged_robot.py:669 lands in commands[:, 3], which nothing reads) */
+
+    /* ABI 7: legged_gym's base reward terms (grx_base_reward_term).  Any non-zero scale routes the handle to the *_base entries: the
+       one-wave lower-limb grx_step_kernel_base*, the tree kernels' grx_step_tree{,16}_base*, the generic grx_step_generic_base*. */
+    float base_reward_scale[GRX_NUM_BASE_REWARD_TERMS];   /* raw cfg scale; the library multiplies by dt, as for reward_scale */
+    float tracking_sigma;        /* cfg.rewards.tracking_sigma (legged_robot.py:1351-1358) */
+    float max_contact_force;     /* cfg.rewards.max_contact_force (legged_robot.py:1374-1376) */
+    int32_t command_curriculum;  /* cfg.commands.curriculum (legged_robot.py:395-396, 828-838): on a step that resets envs, the lin_vel_x range widens
+                                    by 0.5 either way (clipped to +-max_curriculum) when the reset envs' mean tracking_lin_vel episode sum per step
+                                    exceeds 0.8 x its scale x dt; that step's resets draw from the new range.  Needs a non-zero tracking_lin_vel
+                                    scale; runs the base entries.  The decision is per handle (per rank) */
+    float max_curriculum;        /* cfg.commands.max_curriculum */
 } grx_config;
 
 typedef enum grx_tensor_id {
@@ -348,6 +382,15 @@ typedef enum grx_tensor_id {
                                  grx_config.publish_rigid_body_states every step, or current after grx_refresh() */
     GRX_T_AVG_FEET_SPEED_RPY, /* f32 (N, 2, 3) sub-step averaged |angular velocity| of the foot links, world axes: avg_feet_speed_rpy
                                  (legged_robot_fftai.py:34, 81, 88, 144); no active reward term reads it */
+    /* ABI 7 (handles with base reward terms; any other handle: GRX_ERR_INVALID_ARGUMENT) */
+    GRX_T_BASE_EPISODE_SUMS,  /* f32 (GRX_NUM_BASE_REWARD_TERMS, N), caller-writable like GRX_T_EPISODE_SUMS */
+    GRX_T_BASE_REWARD_TERMS,  /* f32 (GRX_NUM_BASE_REWARD_TERMS, N) last step's r_i*scale_i*dt, under publish_reward_terms */
+    GRX_T_BASE_EPISODE_STATS, /* f32 (GRX_NUM_BASE_REWARD_TERMS): GRX_T_EPISODE_STATS' rows of the base terms, current in stream order
+                                 after every launch (a small kernel behind each step and reset) */
+    GRX_T_BASE_EPISODE_STATS_HISTORY, /* f32 (GRX_STATS_HISTORY, GRX_NUM_BASE_REWARD_TERMS): row grx_step_args.stats_slot as for
+                                 GRX_T_EPISODE_STATS_HISTORY */
+    GRX_T_COMMAND_RANGES,     /* f32 (3, 2) device: the current lin_vel_x, lin_vel_y, ang_vel_yaw ranges [lo, hi] the kernels draw commands from
+                                 (handles with command_curriculum only; widened by the curriculum kernel behind a step, in stream order) */
     GRX_NUM_TENSORS
 } grx_tensor_id;
 
@@ -516,6 +559,7 @@ typedef enum grx_struct_id { GRX_STRUCT_CONFIG = 0, GRX_STRUCT_STEP_ARGS = 1, GR
                              GRX_STRUCT_LAYOUT_INFO = 4, GRX_STRUCT_MODEL = 5 } grx_struct_id;
 int grx_sizeof(int struct_id);
 const char* grx_reward_term_name(int term);
+const char* grx_base_reward_term_name(int term);   /* ABI 7: grx_base_reward_term -> cfg name ("action_rate", ...); NULL out of range */
 
 #ifdef __cplusplus
 }

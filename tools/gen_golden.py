@@ -415,26 +415,10 @@ def gen_pipeline(out):
     np.savez(os.path.join(out, "pipeline.npz"), **data)
 
 
-def gen_pipeline_rough(out):
-    """One reference post_physics_step() ON THE ROUGH-TERRAIN RASTER (VERDICT r4 weak #3): the raster of terrain.npz (seed 1,
-    10 x 20 curriculum tiles), the reference's own _get_heights (legged_robot.py:1235-1274) inside the step, so that the 121-entry
-    height block of pri_obs with NON-UNIFORM heights, feet_height = mean(z_foot - h_k) (legged_robot_fftai.py:118-124), the x25
-    scaling (gr1t1.py:281-313, Q5) and base_heights_offset come from the reference on a real raster.  A scan point within fp32
-    rounding of a cell edge may legitimately read the neighbouring cell; poses are redrawn until every point of the env sits at
-    least 5e-4 cells (5e-5 m) from an edge in fp64, so the fixture compares without an allowance."""
-    from legged_gym.utils.terrain import Terrain
-    from legged_gym.envs.base.legged_robot_config import LeggedRobotCfg
+def rough_poses(env, g, tcfg, ter, N):
+    """Poses of gen_pipeline_rough over the reference raster: every scan point at least 5e-4 cells from a cell edge (fp64), base and feet
+    above the local terrain.  Returns the number of redraws."""
     from legged_gym.utils.math import quat_apply_yaw
-    tcfg = LeggedRobotCfg.terrain()
-    tcfg.mesh_type = "heightfield"
-    np.random.seed(1)
-    ter = Terrain(tcfg, 64)          # the raster of terrain.npz (same seed, same call): the tests load it from there
-    N = 64
-    env, g, body_names = make_ref_env(N, 31, terrain_obj=ter)
-    env.cfg.domain_rand.push_robots = False
-    assert env.cfg.terrain.measure_heights
-    noise_u = torch.rand(N, 39, generator=g)
-    randomize_state(env, g, body_names, N, 0)
     hs = torch.tensor(ter.heightsamples.astype(np.int64))
     feet = env.feet_indices
     torso = int(env.torso_indices[0])
@@ -467,6 +451,29 @@ def gen_pipeline_rough(out):
     env.rigid_body_states[:, :, 0:3] = env.root_states[:, None, 0:3]
     env.rigid_body_states[:, feet, 2] = ground[:, None] + torch.rand(N, 2, generator=g) * 0.25
     env.rigid_body_states[:, torso, 3:7] = env.root_states[:, 3:7]
+    return redraws
+
+
+def gen_pipeline_rough(out):
+    """One reference post_physics_step() ON THE ROUGH-TERRAIN RASTER (VERDICT r4 weak #3): the raster of terrain.npz (seed 1,
+    10 x 20 curriculum tiles), the reference's own _get_heights (legged_robot.py:1235-1274) inside the step, so that the 121-entry
+    height block of pri_obs with NON-UNIFORM heights, feet_height = mean(z_foot - h_k) (legged_robot_fftai.py:118-124), the x25
+    scaling (gr1t1.py:281-313, Q5) and base_heights_offset come from the reference on a real raster.  A scan point within fp32
+    rounding of a cell edge may legitimately read the neighbouring cell; poses are redrawn until every point of the env sits at
+    least 5e-4 cells (5e-5 m) from an edge in fp64, so the fixture compares without an allowance."""
+    from legged_gym.utils.terrain import Terrain
+    from legged_gym.envs.base.legged_robot_config import LeggedRobotCfg
+    tcfg = LeggedRobotCfg.terrain()
+    tcfg.mesh_type = "heightfield"
+    np.random.seed(1)
+    ter = Terrain(tcfg, 64)          # the raster of terrain.npz (same seed, same call): the tests load it from there
+    N = 64
+    env, g, body_names = make_ref_env(N, 31, terrain_obj=ter)
+    env.cfg.domain_rand.push_robots = False
+    assert env.cfg.terrain.measure_heights
+    noise_u = torch.rand(N, 39, generator=g)
+    randomize_state(env, g, body_names, N, 0)
+    redraws = rough_poses(env, g, tcfg, ter, N)
     inp = snapshot_inputs(env)
     env.reset_idx = lambda ids: None
     orig_rand_like = torch.rand_like
@@ -602,6 +609,126 @@ def gen_reward_terms(out):
         vals[n] = (v.float() if torch.is_tensor(v) else torch.full((N,), float(v))).numpy().copy()
     np.savez(os.path.join(out, "reward_terms.npz"), names=np.array(names), values=np.stack([vals[n] for n in names]),
              **{"in_" + k: v for k, v in inp.items()})
+
+
+# legged_gym's base reward terms (legged_robot.py:1277-1376) the FFTAI / GR1 classes do not override, with the scales
+# base_reward_terms.npz enables next to the registered GR1T1 ones (legged_gym's own defaults where it has one)
+BASE_TERM_SCALES = {"action_rate": -0.01, "ang_vel_xy": -0.05, "base_height": -1.0, "dof_acc": -2.5e-7, "dof_pos_limits": -10.0,
+                    "dof_vel": -1e-4, "dof_vel_limits": -1.0, "feet_contact_forces": -0.01, "lin_vel_z": -2.0, "orientation": -1.0,
+                    "stumble": -0.5, "torque_limits": -0.1, "torques": -1e-5, "tracking_ang_vel": 0.5, "tracking_lin_vel": 1.0}
+
+
+def gen_base_reward_terms(out):
+    """legged_gym's 15 base reward terms and compute_reward's total, from the reference's own post_physics_step with every base term at a
+    non-zero scale next to the registered GR1T1 scales: on the plane and on the reference raster (base_height reads this step's scan).
+    Rows are set so that every threshold is crossed by some rows and not by others."""
+    from legged_gym.utils.terrain import Terrain
+    from legged_gym.envs.base.legged_robot_config import LeggedRobotCfg
+    from legged_gym.utils.helpers import class_to_dict
+    names = sorted(BASE_TERM_SCALES)
+    data = {"names": np.array(names), "scales": np.array([BASE_TERM_SCALES[n] for n in names])}
+    N = 64
+    for case in ("plane", "rough"):
+        if case == "rough":
+            tcfg = LeggedRobotCfg.terrain()
+            tcfg.mesh_type = "heightfield"
+            np.random.seed(1)
+            ter = Terrain(tcfg, 64)   # the raster of terrain.npz
+            env, g, body_names = make_ref_env(N, 43, terrain_obj=ter)
+        else:
+            env, g, body_names = make_ref_env(N, 41)
+        if case == "plane":   # every _reward_* the reference's GR1T1 class resolves (its own and LeggedRobot's)
+            data["resolvable"] = np.array(sorted(n[len("_reward_"):] for n in dir(type(env)) if n.startswith("_reward_")))
+        for n, v in BASE_TERM_SCALES.items():
+            setattr(env.cfg.rewards.scales, n, v)
+        env.reward_scales = class_to_dict(env.cfg.rewards.scales)
+        env._prepare_reward_function()
+        env.cfg.domain_rand.push_robots = False
+        noise_u = torch.rand(N, 39, generator=g)
+        randomize_state(env, g, body_names, N, 0)
+        if case == "rough":
+            rough_poses(env, g, tcfg, ter, N)
+        feet = env.feet_indices
+        # threshold rows: |F| above max_contact_force, stumble on either side of |F_xy| = 5 |F_z|, a foot in the air with a sideways force
+        fmax = env.cfg.rewards.max_contact_force
+        env.contact_forces[13, feet[0]] = torch.tensor([30.0, 0.0, fmax + 200.0])
+        env.contact_forces[14, feet[1]] = torch.tensor([0.0, 0.0, fmax - 50.0])
+        env.contact_forces[15, feet[0]] = torch.tensor([60.0, 0.0, 10.0])    # |F_xy| = 6 |F_z|: stumble
+        env.contact_forces[16, feet[1]] = torch.tensor([40.0, 0.0, 10.0])    # 4 |F_z|: no stumble
+        env.contact_forces[17, feet[0]] = torch.tensor([0.0, 5.0, 0.0])      # F_z = 0: stumble
+        env.commands[18, :2] = torch.tensor([0.07, 0.07])                    # |cmd_xy| just below 0.1
+        env.commands[19, :2] = torch.tensor([0.08, 0.07])                    # just above
+        inp = snapshot_inputs(env)
+        vals = {}
+        orig_reward = env.compute_reward
+
+        def compute_reward():   # the terms as compute_reward sees them (after the state update, timers and this step's scan)
+            for n in names:
+                vals[n] = getattr(env, "_reward_" + n)().float().numpy().copy()
+            vals["measured_heights"] = (env.measured_heights * torch.ones(N, 1)).numpy().copy() if not torch.is_tensor(env.measured_heights) \
+                else env.measured_heights.numpy().copy()
+            orig_reward()
+        env.compute_reward = compute_reward
+        # _reward_orientation (legged_robot.py:1287) reads self.projected_gravity, an attribute this fork renamed to base_projected_gravity
+        # (legged_robot.py:165, 311): the reference raises AttributeError with orientation enabled.  The fixture evaluates the term's
+        # formula on the renamed buffer (the same tensor, updated in place by the step).
+        env.projected_gravity = env.base_projected_gravity
+        env.reset_idx = lambda ids: None
+        orig_rand_like = torch.rand_like
+        torch.rand_like = lambda t, _u=noise_u: _u.clone()
+        try:
+            env.post_physics_step()
+        finally:
+            torch.rand_like = orig_rand_like
+        v = np.stack([vals[n] for n in names])
+        # every threshold is crossed by some rows and not by others
+        for n in ("dof_pos_limits", "torque_limits", "feet_contact_forces", "stumble"):
+            k = names.index(n)
+            assert (v[k] > 0).any() and (v[k] == 0).any(), n
+        k = names.index("dof_vel_limits")
+        per_joint = (env.dof_vel.abs() - env.dof_vel_limits * env.cfg.rewards.soft_dof_vel_limit)
+        assert (v[k] > 0).any() and (v[k] == 0).any() and (per_joint > 1).any() and ((per_joint > 0) & (per_joint < 1)).any()
+        assert ((env.commands[:, :2].norm(dim=1) > 0.1) & (env.commands[:, :2].norm(dim=1) < 0.12)).any()
+        assert ((env.commands[:, :2].norm(dim=1) < 0.1) & (env.commands[:, :2].norm(dim=1) > 0.08)).any()
+        data[case + "_values"] = v
+        data[case + "_rew"] = env.rew_buf.numpy().copy()
+        data[case + "_measured_heights"] = vals["measured_heights"]
+        data[case + "_reward_names"] = np.array(env.reward_names)
+        data[case + "_episode_sums"] = np.stack([env.episode_sums[n].numpy().copy() for n in env.reward_names])
+        data[case + "_noise_u"] = noise_u.numpy()
+        data.update({case + "_in_" + k_: x for k_, x in inp.items()})
+    np.savez_compressed(os.path.join(out, "base_reward_terms.npz"), **data)
+
+
+def gen_command_curriculum(out):
+    """The reference's update_command_curriculum (legged_robot.py:828-838) on a sequence of reset sets and tracking_lin_vel episode sums:
+    an asymmetric start range, a max_curriculum that is not a multiple of 0.5, means just below and just above the 0.8 threshold, the
+    clip at +-max_curriculum.  No RNG in this arithmetic."""
+    N = 64
+    env, g, _ = make_ref_env(N, 47)
+    env.cfg.commands.max_curriculum = 1.7
+    env.command_ranges["lin_vel_x"] = [-0.3, 0.7]
+    env.reward_scales["tracking_lin_vel"] = 1.0 * env.dt
+    env.episode_sums = {"tracking_lin_vel": torch.zeros(N)}
+    thr = 0.8 * env.reward_scales["tracking_lin_vel"] * float(env.max_episode_length)   # mean episode sum at the threshold
+    # (relative offset of the chosen envs' mean from the threshold, how many envs reset)
+    plan = [(+0.30, 3), (-0.001, 5), (+0.001, 4), (-0.40, 1), (+0.25, 7), (+0.50, 2), (+0.001, 6), (+0.20, 3)]
+    ids_all, sums_all, ranges = [], [], []
+    for rel, k in plan:
+        ids = torch.randperm(N, generator=g)[:k].sort().values
+        mean = thr * (1.0 + rel)
+        spread = (torch.rand(k, generator=g) - 0.5) * 0.2 * thr
+        spread -= spread.mean()
+        sums = torch.full((N,), 0.5 * thr)
+        sums[ids] = (mean + spread).float()
+        env.episode_sums["tracking_lin_vel"] = sums
+        env.update_command_curriculum(ids)
+        ids_all.append(np.isin(np.arange(N), ids.numpy()))
+        sums_all.append(sums.numpy().copy())
+        ranges.append(np.array(env.command_ranges["lin_vel_x"], dtype=np.float64))
+    np.savez(os.path.join(out, "command_curriculum.npz"), reset=np.stack(ids_all), sums=np.stack(sums_all), lin_vel_x=np.stack(ranges),
+             start=np.array([-0.3, 0.7]), max_curriculum=1.7, scale_dt=env.reward_scales["tracking_lin_vel"],
+             max_episode_length=float(env.max_episode_length), dt=env.dt)
 
 
 def gen_terrain_and_heights(out):
@@ -753,6 +880,8 @@ def main():
     gen_pipeline_rough(OUT)
     gen_pipeline_other_robots(OUT)
     gen_reward_terms(OUT)
+    gen_base_reward_terms(OUT)
+    gen_command_curriculum(OUT)
     gen_terrain_and_heights(OUT)
     gen_terrain_all_tiles(OUT)
     gen_trimesh_tiles(OUT)

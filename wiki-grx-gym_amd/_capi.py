@@ -5,7 +5,7 @@ Field order and sizes must match the header exactly; ``grx_create`` rejects a mi
 """
 import ctypes as C
 
-GRX_ABI_VERSION = 6
+GRX_ABI_VERSION = 7
 PUBLISH_NEVER, PUBLISH_EVERY_STEP, PUBLISH_ON_REFRESH = 0, 1, 2   # grx_publish_mode
 CONTROL_TYPES = {"P": 0, "V": 1, "T": 2}   # grx_control_type (legged_robot.py:693-707)
 MAX_BODIES = 36
@@ -30,6 +30,14 @@ REWARD_TERMS = (
 )
 NUM_REWARD_TERMS = len(REWARD_TERMS)
 assert list(REWARD_TERMS) == sorted(REWARD_TERMS)  # alphabetical == the reference's dir() order
+# ABI 7: legged_gym's base reward terms (legged_robot.py:1277-1376) the FFTAI / GR1 classes do not override (grx_base_reward_term)
+BASE_REWARD_TERMS = (
+    "action_rate", "ang_vel_xy", "base_height", "dof_acc", "dof_pos_limits", "dof_vel", "dof_vel_limits",
+    "feet_contact_forces", "lin_vel_z", "orientation", "stumble", "torque_limits", "torques", "tracking_ang_vel",
+    "tracking_lin_vel",
+)
+NUM_BASE_REWARD_TERMS = len(BASE_REWARD_TERMS)
+assert list(BASE_REWARD_TERMS) == sorted(BASE_REWARD_TERMS) and not set(BASE_REWARD_TERMS) & set(REWARD_TERMS)
 
 SPH_FOOT_LEFT, SPH_FOOT_RIGHT, SPH_TERMINATE, SPH_PENALISE = 1, 2, 4, 8
 TERRAIN_PLANE, TERRAIN_HEIGHTFIELD = 0, 1
@@ -42,6 +50,8 @@ TENSOR_IDS = (
     "MEASURED_HEIGHTS", "BASE_HEIGHTS_OFFSET", "EPISODE_SUMS", "REWARD_TERMS", "TERRAIN_LEVELS",
     "TERRAIN_TYPES", "ENV_ORIGINS", "MOTOR_STRENGTH", "FRICTION", "BASE_MASS_COM", "TERM_CONTACT",
     "EPISODE_STATS", "ANCHORS", "CONTACT_FORCES", "EPISODE_STATS_HISTORY", "RIGID_BODY_STATES", "AVG_FEET_SPEED_RPY",
+    "BASE_EPISODE_SUMS", "BASE_REWARD_TERMS", "BASE_EPISODE_STATS", "BASE_EPISODE_STATS_HISTORY",   # ABI 7: handles with base reward terms
+    "COMMAND_RANGES",                                                                                  # ABI 7: handles with the command curriculum
 )
 T = {name: i for i, name in enumerate(TENSOR_IDS)}
 DTYPE_F32, DTYPE_U8, DTYPE_I32, DTYPE_I64 = 0, 1, 2, 3
@@ -144,6 +154,10 @@ class Config(C.Structure):
         ("publish_rigid_body_states", i32),
         ("publish_measured_heights", i32),
         ("control_type", i32), ("heading_command", i32),
+        # ABI 7
+        ("base_reward_scale", f32 * NUM_BASE_REWARD_TERMS),
+        ("tracking_sigma", f32), ("max_contact_force", f32),
+        ("command_curriculum", i32), ("max_curriculum", f32),
     ]
 
 
@@ -204,6 +218,8 @@ def bind(lib, prefix="grx_"):
         "abi_version": fn("abi_version", C.c_int),
         "reward_term_name": fn("reward_term_name", C.c_char_p, C.c_int),
     }
+    if hasattr(lib, prefix + "base_reward_term_name"):
+        api["base_reward_term_name"] = fn("base_reward_term_name", C.c_char_p, C.c_int)
     if hasattr(lib, prefix + "debug_post_physics") and prefix == "grx_":   # the oracle's entry of that name is per-env (oracle/binding.py)
         api["debug_post_physics"] = fn("debug_post_physics", C.c_int, H, C.POINTER(PipelineState), C.c_int, C.POINTER(StepArgs), C.c_void_p)
     if hasattr(lib, prefix + "wait_idle"):
@@ -231,6 +247,7 @@ EXPORTED_SYMBOLS = (
     "grx_create", "grx_destroy", "grx_reset_all", "grx_step", "grx_tensor", "grx_set_state",
     "grx_episode_stats", "grx_flush_stats", "grx_reset_idx", "grx_set_state_indexed", "grx_kernel_time_ms", "grx_wait_idle", "grx_last_error", "grx_abi_version",
     "grx_reward_term_name", "grx_debug_post_physics", "grx_layout", "grx_stats_seq", "grx_debug_spin_report", "grx_sizeof", "grx_refresh", "grx_debug_terrain", "grx_debug_wall", "grx_debug_trimesh_tables",
+    "grx_base_reward_term_name",
 )
 # grx_struct_id (include/grx.h): grx_sizeof(id) must equal ctypes.sizeof of the mirror -- checked once per process by sim.load_hip_library
 STRUCT_IDS = {"CONFIG": (0, Config), "STEP_ARGS": (1, StepArgs), "TENSOR_DESC": (2, TensorDesc), "PIPELINE_STATE": (3, PipelineState),

@@ -27,23 +27,23 @@ int grx_envs_per_block_quad(void);
 void grx_launch_finalize(const KParams* dP, long long seq, long long* progress, long long ticket, hipStream_t stream);
 void grx_launch_ticket(long long* progress, long long ticket, hipStream_t stream);
 int grx_launch_step_generic(const KParams* dP, const void* tables, float* ws, int N, int epb, int lds_bytes, int heightfield, const float* actions,
-                            float delay, long long common_step, const float* noise, float* obs_out, float* pri_out, long long seq, hipStream_t stream);
+                            float delay, long long common_step, const float* noise, float* obs_out, float* pri_out, long long seq, int base, hipStream_t stream);
 void grx_launch_reset_all_generic(const KParams* dP, const void* tables, int N, int epb, uint32_t step, long long seq, uint8_t* mask, hipStream_t stream);
 int grx_generic_tables_size(void);
 int grx_tree_lds_bytes(int nb, int nlc, int nchain, int nsph, int waves);
 int grx_tree_envs_per_wave(void);
 int grx_launch_step_tree(const KParams* dP, const void* tree_tab, const void* gen_tab, int N, int waves, int lds_bytes, int heightfield, const float* actions, float delay,
-                         long long common_step, const float* noise, float* obs_out, float* pri_out, const StepSeq* sq, hipStream_t stream);
+                         long long common_step, const float* noise, float* obs_out, float* pri_out, const StepSeq* sq, int base, hipStream_t stream);
 int grx_launch_step_tree_debug(const KParams* dP, const void* tree_tab, const void* gen_tab, int N, int waves, int lds_bytes, int heightfield, const float* actions,
-                               long long common_step, const float* noise, const float* dbg, const StepSeq* sq, hipStream_t stream);
+                               long long common_step, const float* noise, const float* dbg, const StepSeq* sq, int base, hipStream_t stream);
 int grx_generic_ws_floats_per_env(int nb, int nlc);
 // csrc/grx_tree16.hip: the tree kernel with a 16-lane group per env (four envs per wave)
 int grx_tree_lds_bytes16(int nb, int nlc, int nchain, int nsph, int waves);
 int grx_tree_envs_per_wave16(void);
 int grx_launch_step_tree16(const KParams* dP, const void* tree_tab, const void* gen_tab, int N, int waves, int lds_bytes, int heightfield, const float* actions, float delay,
-                           long long common_step, const float* noise, float* obs_out, float* pri_out, const StepSeq* sq, hipStream_t stream);
+                           long long common_step, const float* noise, float* obs_out, float* pri_out, const StepSeq* sq, int base, hipStream_t stream);
 int grx_launch_step_tree_debug16(const KParams* dP, const void* tree_tab, const void* gen_tab, int N, int waves, int lds_bytes, int heightfield, const float* actions,
-                                 long long common_step, const float* noise, const float* dbg, const StepSeq* sq, hipStream_t stream);
+                                 long long common_step, const float* noise, const float* dbg, const StepSeq* sq, int base, hipStream_t stream);
 void grx_launch_reset_all(const KParams* dP, int N, uint32_t step, const StepSeq* sq, uint8_t* mask, hipStream_t stream);
 void grx_launch_mark(const int32_t* env_ids, int n, int N, uint8_t* mask, hipStream_t stream);
 void grx_launch_set_state(const KParams* dP, int N, const float* root, const float* q, const float* qd, const int32_t* env_ids, int n, hipStream_t stream);
@@ -57,6 +57,14 @@ void grx_launch_step_debug(const KParams* dP, int N, int heightfield, int waves,
 void grx_launch_step_debug_quad(const KParams* dP, int N, int heightfield, int waves, const float* actions, long long common_step, const float* noise,
                                 const float* dbg, const StepSeq* sq, hipStream_t stream);
 int grx_debug_rows(void);
+// ABI 7: the one-wave entries with legged_gym's base reward terms and their statistics kernels
+void grx_launch_step_base(const KParams* dP, int N, int heightfield, const float* actions, float delay, long long common_step,
+                          const float* noise, float* obs_out, float* pri_out, const StepSeq* sq, hipStream_t stream);
+void grx_launch_step_debug_base(const KParams* dP, int N, int heightfield, const float* actions, long long common_step, const float* noise,
+                                const float* dbg, const StepSeq* sq, hipStream_t stream);
+void grx_launch_base_reset(const KParams* dP, int N, const uint8_t* mask, hipStream_t stream);
+void grx_launch_base_stats(const KParams* dP, long long seq, int nb, hipStream_t stream);
+void grx_launch_curriculum(const KParams* dP, int nb, uint32_t step, float* obs, int nobs, float* pri, int npri, hipStream_t stream);
 int grx_debug_row_of(int what);   // 0: torques, 1: last_last_actions, 2: termination contact, 3: apply_reset
 int grx_set_spin_word(unsigned long long* p);
 int grx_set_spin_word_quad(unsigned long long* p);
@@ -113,6 +121,8 @@ struct grx_sim {
     int waves = 1;         // waves per 32-env block of the step kernel (1, 2 or 4)
     bool quad = false;     // four waves, a lane quad per env, 16 envs per block (grx_quad.hip): while the blocks fit the CUs in one round
     bool generic = false;  // model outside the fast kernel's lower-limb topology: generic-tree kernel (grx_generic.h)
+    bool base = false;     // ABI 7: legged_gym's base reward terms active -- the *_base entries of the layout
+    int base_cols = 0;     // ... their statistics columns per launch: one per wave of the step kernel
     int rbs_mode = GRX_PUBLISH_NEVER, heights_mode = GRX_PUBLISH_EVERY_STEP;   // grx_publish_mode of GRX_T_RIGID_BODY_STATES / GRX_T_MEASURED_HEIGHTS
     int nd = GRX_ND;
     void* d_gen = nullptr; // GenTables (device)
@@ -855,6 +865,12 @@ int grx_create(const grx_config* cfg, int device_id, grx_handle* out) {
         armature = armature || m.dof_armature[j] != 0.f;
     }
     bool generic = rc != GRX_OK || armature || getenv("GRX_FORCE_GENERIC") != nullptr;
+    // ABI 7: legged_gym's base reward terms and the command curriculum (which reads tracking_lin_vel) live in the one-wave lower-limb entries only
+    if (c.command_curriculum && c.base_reward_scale[GRX_BREW_TRACKING_LIN_VEL] == 0.f)
+        return fail(GRX_ERR_INVALID_ARGUMENT, "grx_create: command_curriculum needs the tracking_lin_vel reward term (the reference raises KeyError without it)");
+    bool base = false;
+    for (int t = 0; t < GRX_NUM_BASE_REWARD_TERMS; ++t) base = base || c.base_reward_scale[t] != 0.f;
+    if (base && !(c.tracking_sigma > 0.f)) return fail(GRX_ERR_INVALID_ARGUMENT, "grx_create: base reward terms need tracking_sigma > 0");
     // control_type outside {P, V, T}: the reference raises (legged_robot.py:707); a C caller gets the status code (the Python host raises NameError before)
     if (c.control_type != GRX_CONTROL_P && c.control_type != GRX_CONTROL_V && c.control_type != GRX_CONTROL_T)
         return fail(GRX_ERR_INVALID_ARGUMENT, "grx_create: control_type must be GRX_CONTROL_P, _V or _T");
@@ -884,7 +900,7 @@ int grx_create(const grx_config* cfg, int device_id, grx_handle* out) {
     s->cfg.terrain_origins = nullptr;
     s->device = device_id;
     s->N = c.num_envs;
-    s->generic = generic; s->nd = nd;
+    s->generic = generic; s->nd = nd; s->base = base;
     const size_t N = (size_t)c.num_envs;
     KParams& P = s->hp;
     memset(&P, 0, sizeof P);
@@ -911,6 +927,8 @@ int grx_create(const grx_config* cfg, int device_id, grx_handle* out) {
         // control_type 'V' / 'T' and heading_command (ABI 5; off in every registered task) live in the general one-wave layout only:
         // the wave pipelines keep the registered tasks' code path
         if (c.control_type != GRX_CONTROL_P || c.heading_command) { s->quad = false; s->waves = 1; }
+        // so do legged_gym's base reward terms (ABI 7), in entries of their own
+        if (base) { s->quad = false; s->waves = 1; }
     }
     const char* dbg = getenv("GRX_PUBLISH_DEBUG");   // (tools/: overrides the config either way)
     P.publish_debug = dbg ? atoi(dbg) : c.publish_reward_terms;
@@ -935,6 +953,9 @@ int grx_create(const grx_config* cfg, int device_id, grx_handle* out) {
     const float dtp = c.sim_dt * (float)c.decimation;
     for (int t = 0; t < NT; ++t) { P.reward_scale_dt[t] = c.reward_scale[t] * dtp; P.reward_sigma[t] = c.reward_sigma[t]; }
     P.only_positive_rewards = c.only_positive_rewards;
+    for (int t = 0; t < GRX_NUM_BASE_REWARD_TERMS; ++t) { P.base_scale_dt[t] = c.base_reward_scale[t] * dtp; if (c.base_reward_scale[t] != 0.f) P.base_active |= 1u << t; }
+    P.tracking_sigma = c.tracking_sigma; P.max_contact_force = c.max_contact_force;
+    P.command_curriculum = c.command_curriculum ? 1 : 0; P.max_curriculum = c.max_curriculum;
     P.base_height_target = c.base_height_target; P.swing_feet_height_target = c.swing_feet_height_target;
     P.feet_stumble_ratio = c.feet_stumble_ratio; P.feet_air_time_target = c.feet_air_time_target; P.feet_land_time_max = c.feet_land_time_max;
     P.soft_dof_vel_limit = c.soft_dof_vel_limit; P.soft_torque_limit = c.soft_torque_limit;
@@ -978,6 +999,12 @@ int grx_create(const grx_config* cfg, int device_id, grx_handle* out) {
     P.stat_stride = (generic ? 8 : 2) * nblocks + 1;
     DA(stat_partial, (size_t)2 * NSTAT * P.stat_stride); DA(stat_nblocks, 2); DA(stat_hist, (size_t)GRX_STATS_HISTORY * NSTAT);
     DA(stats, NSTAT); DA(prof, (size_t)std::max(2 * nblocks, 64) * GRX_PROF_SLOTS);   // (16-env blocks in the quad layout; the tree kernel stamps blocks 0..63 whatever their size)
+    s->base_cols = nblocks;   // (the fused one-wave entry: a wave per 32-env block; the tree / generic kernels: set with their tables below)
+    if (base) {
+        constexpr int NB = GRX_NUM_BASE_REWARD_TERMS;
+        DA(base_episode_sums, NB * N); DA(base_reward_terms, NB * N);
+        DA(base_stat_partial, (size_t)(NB + 1) * P.stat_stride); DA(base_stats, NB); DA(base_stat_hist, (size_t)GRX_STATS_HISTORY * NB);
+    }
     rc = dalloc(s, &s->d_mask, N);
     if (rc) { grx_destroy(s); return rc; }
     if (c.publish_rigid_body_states < 0 || c.publish_rigid_body_states > 2 || c.publish_measured_heights < 0 || c.publish_measured_heights > 2) {
@@ -1262,6 +1289,12 @@ int grx_create(const grx_config* cfg, int device_id, grx_handle* out) {
     desc_vec(s, GRX_T_TERM_CONTACT, P.term_contact, GRX_U8, Ni);
     desc_vec(s, GRX_T_EPISODE_STATS, P.stats, GRX_F32, NSTAT);
     desc_rows(s, GRX_T_EPISODE_STATS_HISTORY, P.stat_hist, GRX_STATS_HISTORY, NSTAT);
+    if (s->base) {   // (ABI 7; a handle without base terms has no such tensors: data stays NULL, grx_tensor refuses them)
+        desc_rows(s, GRX_T_BASE_EPISODE_SUMS, P.base_episode_sums, GRX_NUM_BASE_REWARD_TERMS, Ni);
+        desc_rows(s, GRX_T_BASE_REWARD_TERMS, P.base_reward_terms, GRX_NUM_BASE_REWARD_TERMS, Ni);
+        desc_vec(s, GRX_T_BASE_EPISODE_STATS, P.base_stats, GRX_F32, GRX_NUM_BASE_REWARD_TERMS);
+        desc_rows(s, GRX_T_BASE_EPISODE_STATS_HISTORY, P.base_stat_hist, GRX_STATS_HISTORY, GRX_NUM_BASE_REWARD_TERMS);
+    }
     desc_soa3(s, GRX_T_ANCHORS, P.anchors, 8, 3);
     desc_soa3(s, GRX_T_CONTACT_FORCES, P.contact_forces, GRX_MAX_LINKS, 3);
     desc_soa3(s, GRX_T_RIGID_BODY_STATES, P.rbs, GRX_MAX_LINKS, 13);
@@ -1282,6 +1315,11 @@ int grx_create(const grx_config* cfg, int device_id, grx_handle* out) {
     if (generic) {
         rc = build_generic(s, c);
         if (rc) { grx_destroy(s); return rc; }
+        if (s->d_tree) {
+            const int epw = s->tree_g == GRX_TREE_GMAX ? grx_tree_envs_per_wave16() : grx_tree_envs_per_wave();
+            s->base_cols = (s->N + epw * s->tree_waves - 1) / (epw * s->tree_waves) * s->tree_waves;
+        } else s->base_cols = (s->N + s->gen_epb - 1) / s->gen_epb;
+        if (s->base_cols > s->hp.stat_stride) { grx_destroy(s); return fail(GRX_ERR_UNSUPPORTED_MODEL, "grx_create: more statistics columns than the table holds"); }
         if (!s->d_tree) {   // the one-lane generic kernel (trees with more than eight chains): no link frames, neither every step nor on refresh (it does not stash the state before a reset)
             s->hp.publish_rbs = 0;
             if (s->rbs_mode == GRX_PUBLISH_EVERY_STEP) { s->rbs_mode = GRX_PUBLISH_NEVER; s->desc[GRX_T_RIGID_BODY_STATES].data = nullptr; }
@@ -1303,10 +1341,17 @@ int grx_create(const grx_config* cfg, int device_id, grx_handle* out) {
         s->spin_bounded = grx_set_spin_word(reinterpret_cast<unsigned long long*>(s->pace.d_progress + 1)) == 1;
         grx_set_spin_word_quad(reinterpret_cast<unsigned long long*>(s->pace.d_progress + 1));
     }
-    {   // the parameter block is immutable from here on: upload it once
+    {   // the parameter block is immutable from here on -- but for the command ranges of a curriculum handle (grx_curriculum_kernel): upload it once
         rc = dalloc(s, &s->d_hp, 1);
         if (rc) { grx_destroy(s); return rc; }
         HIP_TRY(hipMemcpy(s->d_hp, &s->hp, sizeof(KParams), hipMemcpyHostToDevice));
+        if (s->hp.command_curriculum) {   // the ranges the kernels draw from ARE the device copy's (the curriculum kernel widens them there)
+            grx_tensor_desc& d = s->desc[GRX_T_COMMAND_RANGES];
+            d.data = reinterpret_cast<char*>(s->d_hp) + offsetof(KParams, cmd_lin_vel_x);
+            d.dtype = GRX_F32; d.ndim = 2; d.shape[0] = 3; d.shape[1] = 2; d.stride[0] = 2; d.stride[1] = 1;
+            static_assert(offsetof(KParams, cmd_lin_vel_y) == offsetof(KParams, cmd_lin_vel_x) + 2 * sizeof(float) &&
+                          offsetof(KParams, cmd_ang_vel_yaw) == offsetof(KParams, cmd_lin_vel_x) + 4 * sizeof(float), "the three ranges must be one (3, 2) block");
+        }
     }
     *out = s;
     return GRX_OK;
@@ -1386,6 +1431,7 @@ int grx_reset_all(grx_handle s, void* stream) {
     // (the generic reset kernel does not fold its predecessor's statistics: reduce them now)
     if (s->generic && !s->stats_current) grx_launch_finalize(s->d_hp, s->eager_seq, nullptr, 0, st);
     const StepSeq q = next_seq(s, st, capturing);
+    if (s->base) grx_launch_base_reset(s->d_hp, s->N, nullptr, st);   // ABI 7: the base terms' sums of the finished episodes (every layout)
     if (s->generic) {
         grx_launch_reset_all_generic(s->d_hp, s->d_gen, s->N, s->gen_epb, step, q.seq, nullptr, st);
         grx_launch_finalize(s->d_hp, q.seq, q.progress, q.progress ? s->pace.issued : 0, st);
@@ -1394,6 +1440,7 @@ int grx_reset_all(grx_handle s, void* stream) {
         grx_launch_reset_all(s->d_hp, s->N, step, &q, nullptr, st);
         if (capturing) grx_launch_finalize(s->d_hp, q.seq, nullptr, 0, st);   // recorded into a graph: carries its own reduction, see grx_step
     }
+    if (s->base) grx_launch_base_stats(s->d_hp, q.seq, (s->N + 63) / 64, st);
     HIP_TRY(hipGetLastError());
     return GRX_OK;
 }
@@ -1410,6 +1457,7 @@ int grx_reset_idx(grx_handle s, const int32_t* env_ids, int32_t n, void* stream)
     if (s->generic && !s->stats_current) grx_launch_finalize(s->d_hp, s->eager_seq, nullptr, 0, st);
     const StepSeq q = next_seq(s, st, capturing);
     grx_launch_mark(env_ids, n, s->N, s->d_mask, st);
+    if (s->base) grx_launch_base_reset(s->d_hp, s->N, s->d_mask, st);   // (before the reset kernel consumes the flags; every layout)
     if (s->generic) {
         grx_launch_reset_all_generic(s->d_hp, s->d_gen, s->N, s->gen_epb, step, q.seq, s->d_mask, st);
         grx_launch_finalize(s->d_hp, q.seq, q.progress, q.progress ? s->pace.issued : 0, st);
@@ -1418,6 +1466,7 @@ int grx_reset_idx(grx_handle s, const int32_t* env_ids, int32_t n, void* stream)
         grx_launch_reset_all(s->d_hp, s->N, step, &q, s->d_mask, st);
         if (capturing) grx_launch_finalize(s->d_hp, q.seq, nullptr, 0, st);
     }
+    if (s->base) grx_launch_base_stats(s->d_hp, q.seq, (s->N + 63) / 64, st);
     HIP_TRY(hipGetLastError());
     return GRX_OK;
 }
@@ -1465,18 +1514,26 @@ int grx_step(grx_handle s, grx_step_args* a, void* stream) {
     {
         if (s->d_tree) {
             if ((s->tree_g == GRX_TREE_GMAX ? grx_launch_step_tree16 : grx_launch_step_tree)(s->d_hp, s->d_tree, s->d_gen, s->N, s->tree_waves, s->tree_lds, terrain_mode(s), a->actions, a->delay_substeps,
-                                     (long long)a->common_step_counter, a->noise_uniform, a->obs_out, a->pri_obs_out, &q, st))
+                                     (long long)a->common_step_counter, a->noise_uniform, a->obs_out, a->pri_obs_out, &q, s->base ? 1 : 0, st))
                 return fail(GRX_ERR_HIP, "grx_step: cannot raise the dynamic LDS limit of the tree kernel");
         } else if (grx_launch_step_generic(s->d_hp, s->d_gen, s->d_ws, s->N, s->gen_epb, s->gen_lds, terrain_mode(s), a->actions,
-                                    a->delay_substeps, (long long)a->common_step_counter, a->noise_uniform, a->obs_out, a->pri_obs_out, q.seq, st))
+                                    a->delay_substeps, (long long)a->common_step_counter, a->noise_uniform, a->obs_out, a->pri_obs_out, q.seq, s->base ? 1 : 0, st))
             return fail(GRX_ERR_HIP, "grx_step: cannot raise the dynamic LDS limit of the generic kernel");
     }
     else
     {
-        if (s->quad) grx_launch_step_quad(s->d_hp, s->N, terrain_mode(s), s->waves, a->actions, a->delay_substeps,
+        if (s->base) grx_launch_step_base(s->d_hp, s->N, terrain_mode(s), a->actions, a->delay_substeps, (long long)a->common_step_counter, a->noise_uniform,
+                                          a->obs_out, a->pri_obs_out, &q, st);   // ABI 7: legged_gym's base reward terms (one wave per block)
+        else if (s->quad) grx_launch_step_quad(s->d_hp, s->N, terrain_mode(s), s->waves, a->actions, a->delay_substeps,
                                           (long long)a->common_step_counter, a->noise_uniform, a->obs_out, a->pri_obs_out, &q, st);
         else grx_launch_step(s->d_hp, s->N, terrain_mode(s), s->waves, a->actions, a->delay_substeps,
                              (long long)a->common_step_counter, a->noise_uniform, a->obs_out, a->pri_obs_out, &q, st);
+    }
+    if (s->base) {   // the base terms' episode statistics right behind the step, then the command curriculum (one block; returns at once on a step without resets)
+        grx_launch_base_stats(s->d_hp, q.seq, s->base_cols, st);
+        if (s->hp.command_curriculum)
+            grx_launch_curriculum(s->d_hp, s->base_cols, (uint32_t)a->common_step_counter, a->obs_out ? a->obs_out : s->hp.obs, s->cfg.num_obs,
+                                  a->pri_obs_out ? a->pri_obs_out : s->hp.pri_obs, s->cfg.num_pri_obs, st);
     }
     if (timed) {
         HIP_TRY(hipEventRecord(ev.second, st));
@@ -1523,6 +1580,8 @@ int grx_refresh(grx_handle s, int id, void* stream) {
 int grx_tensor(grx_handle s, int id, grx_tensor_desc* out) {
     if (!s || !out) return fail(GRX_ERR_INVALID_ARGUMENT, "grx_tensor: null argument");
     if (id < 0 || id >= GRX_NUM_TENSORS) return fail(GRX_ERR_INVALID_ARGUMENT, "grx_tensor: unknown tensor id");
+    if (id == GRX_T_COMMAND_RANGES && !s->hp.command_curriculum) return fail(GRX_ERR_INVALID_ARGUMENT, "grx_tensor: GRX_T_COMMAND_RANGES exists on handles with command_curriculum only");
+    if (id >= GRX_T_BASE_EPISODE_SUMS && !s->base) return fail(GRX_ERR_INVALID_ARGUMENT, "grx_tensor: the base reward term tensors exist on handles with base reward terms only");
     *out = s->desc[id];
     return GRX_OK;
 }
@@ -1577,12 +1636,19 @@ int grx_layout(grx_handle s, grx_layout_info* out) {
     const bool tm = terrain_mode(s) == 2;   // mesh_type 'trimesh': the *_trimesh entries of the same kernels
     if (s->generic && s->d_tree) {
         out->lanes_per_env = s->tree_g; out->waves_per_block = s->tree_waves; out->envs_per_block = (s->tree_g == GRX_TREE_GMAX ? grx_tree_envs_per_wave16() : grx_tree_envs_per_wave()) * s->tree_waves;
-        if (tm) snprintf(out->kernel, sizeof out->kernel, s->tree_g == GRX_TREE_GMAX ? "grx_step_tree16_trimesh<false>" : "grx_step_tree_trimesh<false>");
-        else snprintf(out->kernel, sizeof out->kernel, s->tree_g == GRX_TREE_GMAX ? "grx_step_tree16<%s, false>" : "grx_step_tree<%s, false>", hf);
+        const char* t = s->tree_g == GRX_TREE_GMAX ? "grx_step_tree16" : "grx_step_tree";
+        const char* b = s->base ? "_base" : "";   // (ABI 7: the entries with legged_gym's base reward terms)
+        if (tm) snprintf(out->kernel, sizeof out->kernel, "%s%s_trimesh<false>", t, b);
+        else snprintf(out->kernel, sizeof out->kernel, "%s%s<%s, false>", t, b, hf);
     } else if (s->generic) {
         out->lanes_per_env = 1; out->waves_per_block = 1; out->envs_per_block = s->gen_epb;
-        if (tm) snprintf(out->kernel, sizeof out->kernel, "grx_step_generic_trimesh");
-        else snprintf(out->kernel, sizeof out->kernel, "grx_step_generic<%s>", hf);
+        const char* b = s->base ? "_base" : "";
+        if (tm) snprintf(out->kernel, sizeof out->kernel, "grx_step_generic%s_trimesh", b);
+        else snprintf(out->kernel, sizeof out->kernel, "grx_step_generic%s<%s>", b, hf);
+    } else if (s->base) {
+        out->lanes_per_env = 2; out->waves_per_block = 1; out->envs_per_block = grx_envs_per_block();
+        if (tm) snprintf(out->kernel, sizeof out->kernel, "grx_step_kernel_base_trimesh<false>");
+        else snprintf(out->kernel, sizeof out->kernel, "grx_step_kernel_base<%s, false>", hf);
     } else if (s->quad) {
         out->lanes_per_env = 4; out->waves_per_block = s->waves; out->envs_per_block = grx_envs_per_block_quad();
         if (tm) snprintf(out->kernel, sizeof out->kernel, "grx_step_kernel_quad_trimesh<%d, false>", s->waves);
@@ -1673,12 +1739,14 @@ int grx_debug_post_physics(grx_handle s, const grx_pipeline_state* ps, int apply
     // the post-physics half of the kernel this handle steps with (lane pairs: 1 / 4 / 8 waves; lane quads: 4 / 8; GRX_FORCE_GENERIC: the tree kernel)
     if (s->generic) {
         if ((s->tree_g == GRX_TREE_GMAX ? grx_launch_step_tree_debug16 : grx_launch_step_tree_debug)(s->d_hp, s->d_tree, s->d_gen, s->N, s->tree_waves, s->tree_lds, terrain_mode(s), s->d_dbg_actions,
-                                       (long long)a->common_step_counter, a->noise_uniform, s->d_dbg, &sq, st))
+                                       (long long)a->common_step_counter, a->noise_uniform, s->d_dbg, &sq, s->base ? 1 : 0, st))
             return fail(GRX_ERR_HIP, "grx_debug_post_physics: cannot raise the dynamic LDS limit of the tree kernel");
-    } else if (s->quad) grx_launch_step_debug_quad(s->d_hp, s->N, terrain_mode(s), s->waves, s->d_dbg_actions,
+    } else if (s->base) grx_launch_step_debug_base(s->d_hp, s->N, terrain_mode(s), s->d_dbg_actions, (long long)a->common_step_counter, a->noise_uniform, s->d_dbg, &sq, st);
+    else if (s->quad) grx_launch_step_debug_quad(s->d_hp, s->N, terrain_mode(s), s->waves, s->d_dbg_actions,
                                             (long long)a->common_step_counter, a->noise_uniform, s->d_dbg, &sq, st);
     else grx_launch_step_debug(s->d_hp, s->N, terrain_mode(s), s->waves, s->d_dbg_actions, (long long)a->common_step_counter,
                                a->noise_uniform, s->d_dbg, &sq, st);
+    if (s->base) grx_launch_base_stats(s->d_hp, sq.seq, s->base_cols, st);
     HIP_TRY(hipGetLastError());
     return GRX_OK;
 }
@@ -1766,6 +1834,13 @@ const char* grx_reward_term_name(int t) {
         "limits_dof_pos", "limits_dof_tor", "limits_dof_vel", "on_the_air", "pose_offset", "pose_offset_hip_yaw",
         "stand_still", "termination"};
     return (t >= 0 && t < NT) ? names[t] : "";
+}
+
+const char* grx_base_reward_term_name(int t) {
+    static const char* names[GRX_NUM_BASE_REWARD_TERMS] = {
+        "action_rate", "ang_vel_xy", "base_height", "dof_acc", "dof_pos_limits", "dof_vel", "dof_vel_limits", "feet_contact_forces",
+        "lin_vel_z", "orientation", "stumble", "torque_limits", "torques", "tracking_ang_vel", "tracking_lin_vel"};
+    return (t >= 0 && t < GRX_NUM_BASE_REWARD_TERMS) ? names[t] : nullptr;
 }
 
 }  // extern "C"

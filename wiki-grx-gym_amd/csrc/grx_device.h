@@ -244,4 +244,12 @@ struct KParams {
     const RefreshTab* refresh_tab;
     int32_t nd;        // dofs of the model (10 on the fast path)
     long long* prof;   // GRX_PROFILE_SECTIONS builds only: [nblocks][16] s_memtime stamps
+    // ABI 7: legged_gym's base reward terms (grx_base_reward_term) -- read by the grx_step_kernel_base* entries and their statistics kernels only
+    uint32_t base_active;                                // bit t: base_scale_dt[t] != 0
+    float base_scale_dt[GRX_NUM_BASE_REWARD_TERMS];
+    float tracking_sigma, max_contact_force;
+    float *base_episode_sums, *base_reward_terms;        // [NB][N]
+    float* base_stat_partial;   // [GRX_NUM_BASE_REWARD_TERMS + 1][stat_stride]: per-block sums of the finished episodes' base sums, row NB = their count
+    float *base_stats, *base_stat_hist;                  // [NB], [GRX_STATS_HISTORY][NB]
+    int32_t command_curriculum; float max_curriculum;    // legged_robot.py:828-838 (grx_curriculum_kernel widens cmd_lin_vel_x of the DEVICE copy)
 };

@@ -406,6 +406,17 @@ __global__ __launch_bounds__(64) void grx_step_generic_trimesh(GRX_STEP_GENERIC_
     constexpr int HF = GRX_HF_TRIMESH;
 #include "grx_step_generic_body.inc"
 }
+// ABI 7: the same with legged_gym's base reward terms -- entries of their own
+template <bool HF>
+__global__ __launch_bounds__(64) void grx_step_generic_base(GRX_STEP_GENERIC_ARGS) {
+    constexpr bool kBaseTerms = true;
+#include "grx_step_generic_body.inc"
+}
+__global__ __launch_bounds__(64) void grx_step_generic_base_trimesh(GRX_STEP_GENERIC_ARGS) {
+    constexpr bool kBaseTerms = true;
+    constexpr int HF = GRX_HF_TRIMESH;
+#include "grx_step_generic_body.inc"
+}
 #endif
 
 // BaseTask.reset() first half for the generic path

@@ -67,6 +67,7 @@ namespace {
 
 constexpr int NT = GRX_NUM_REWARD_TERMS;
 constexpr int NSTAT = GRX_NSTAT;
+constexpr bool kBaseTerms = false;   // the step kernel body: legged_gym's base reward terms (shadowed by the grx_step_kernel_base* heads)
 constexpr int LEG = GRX_LEG;
 constexpr int EPB = 64 / LPE;  // envs per block: one wave64 = 32 lane pairs (16 lane quads in grx_quad.hip)
 
@@ -1282,6 +1283,73 @@ GRX_DEV void noise_blocks(KP P, uint32_t genv, uint32_t step, int side, U4 nzb[N
 // rows of the debug-injection table ([DBG_ROWS][N], grx_debug_post_physics): see grx_step_kernel's DBG instantiations
 enum DbgRow { DBG_FEET_FORCE = 0, DBG_FEET_POS = 6, DBG_AVG_FORCE = 12, DBG_AVG_SPEED = 14, DBG_TORQUES = 20, DBG_LAST_LAST_ACTIONS = DBG_TORQUES + GRX_MAX_DOFS,
               DBG_TERM_CONTACT = DBG_LAST_LAST_ACTIONS + GRX_MAX_DOFS, DBG_APPLY_RESET = DBG_TERM_CONTACT + 1, DBG_ROWS = DBG_APPLY_RESET + 1 };   // (a row per dof of ANY model: the 32-DOF full body's fixture goes through the tree kernel)
+// ---- legged_gym's base reward terms (LR:1277-1376) for the one-lane generic and the lane-group tree kernels (their *_base entries; the
+// one-wave lower-limb entry: base_reward_and_sums below).  A joint's share of the joint sums; the env's terms from the reduced sums; the
+// episode sums, debug table and the wave's column of base_stat_partial (the caller's lane 0 stores it, every launch).
+constexpr int NB = GRX_NUM_BASE_REWARD_TERMS;
+struct BaseJ { float ar = 0.f, acc = 0.f, vel = 0.f, tor = 0.f, plim = 0.f, vlim = 0.f, tlim = 0.f; };
+GRX_DEV void base_joint(KP P, BaseJ& s, float al, float ac, float q, float qd, float qd_last, float tau, float slo, float shi, float vl, float eff, float dtp) {
+    s.ar += (al - ac) * (al - ac);
+    const float a = (qd - qd_last) / dtp;
+    s.acc += a * a;
+    s.vel += qd * qd;
+    s.tor += tau * tau;
+    s.plim += (q - slo < 0.f ? -(q - slo) : 0.f) + (q - shi > 0.f ? q - shi : 0.f);   // soft limits, one-sided, not squared
+    s.vlim += fminf(fmaxf(fabsf(qd) - vl * P.soft_dof_vel_limit, 0.f), 1.f);
+    s.tlim += fmaxf(fabsf(tau) - eff * P.soft_torque_limit, 0.f);
+}
+GRX_DEV float base_env_terms(KP P, const BaseJ& s, V3 F0, V3 F1, V3 blv, V3 bav, V3 pg, const float cmd[3], float base_z, int lane, float r[NB]) {
+    const float dh = base_z - P.base_height_target;
+    const float ea = cmd[2] - bav.z, ex = cmd[0] - blv.x, ey = cmd[1] - blv.y;
+    auto stumble = [](V3 F) { return sqrtf(F.x * F.x + F.y * F.y) > 5.f * fabsf(F.z); };   // (the literal 5 of LR:1367)
+    auto over = [&](V3 F) { return fmaxf(sqrtf(F.x * F.x + F.y * F.y + F.z * F.z) - P.max_contact_force, 0.f); };
+    r[GRX_BREW_ACTION_RATE] = s.ar;
+    r[GRX_BREW_ANG_VEL_XY] = bav.x * bav.x + bav.y * bav.y;
+    r[GRX_BREW_BASE_HEIGHT] = dh * dh;
+    r[GRX_BREW_DOF_ACC] = s.acc;
+    r[GRX_BREW_DOF_POS_LIMITS] = s.plim;
+    r[GRX_BREW_DOF_VEL] = s.vel;
+    r[GRX_BREW_DOF_VEL_LIMITS] = s.vlim;
+    r[GRX_BREW_FEET_CONTACT_FORCES] = over(F0) + over(F1);
+    r[GRX_BREW_LIN_VEL_Z] = blv.z * blv.z;
+    r[GRX_BREW_ORIENTATION] = pg.x * pg.x + pg.y * pg.y;
+    r[GRX_BREW_STUMBLE] = (stumble(F0) || stumble(F1)) ? 1.f : 0.f;
+    r[GRX_BREW_TORQUE_LIMITS] = s.tlim;
+    r[GRX_BREW_TORQUES] = s.tor;
+    r[GRX_BREW_TRACKING_ANG_VEL] = expf(-(ea * ea) / P.tracking_sigma);
+    r[GRX_BREW_TRACKING_LIN_VEL] = expf(-(ex * ex + ey * ey) / P.tracking_sigma);
+    // (the scales one per lane, lane t holds term t's: 15 scales in scalar registers spill into the vector registers of these kernels)
+    const uint32_t active = P.base_active;
+    const float scale_v = P.base_scale_dt[(lane & 63) < NB ? (lane & 63) : 0];
+    float rew = 0.f;
+#pragma unroll
+    for (int t = 0; t < NB; ++t) {
+        r[t] = ((active >> t) & 1u) ? r[t] * __int_as_float(__builtin_amdgcn_readlane(__float_as_int(scale_v), t)) : 0.f;
+        rew += r[t];
+    }
+    return rew;
+}
+GRX_DEV void base_env_store(KP P, const float r[NB], int e, int N, bool reset, bool zero_sums, bool writer, int lane, int col) {
+    const uint32_t active = P.base_active;
+    const unsigned long long reset_mask = __ballot(reset && writer);
+    float* const colp = P.base_stat_partial + col;
+#pragma unroll
+    for (int t = 0; t < NB; ++t) {
+        float acc = 0.f;
+        if ((active >> t) & 1u) {   // uniform
+            const float es = P.base_episode_sums[(size_t)t * N + e] + r[t];
+            unsigned long long m = reset_mask;
+            while (m) { const int L = __ffsll((long long)m) - 1; m &= m - 1; acc += __shfl(es, L); }
+            if (writer) {
+                P.base_episode_sums[(size_t)t * N + e] = zero_sums ? 0.f : es;
+                if (P.publish_debug) P.base_reward_terms[(size_t)t * N + e] = r[t];
+            }
+        }
+        if (lane == 0) colp[(size_t)t * P.stat_stride] = acc;
+    }
+    if (lane == 0) colp[(size_t)NB * P.stat_stride] = (float)__popcll(reset_mask);
+}
+
 #ifndef GRX_QUAD_TU
 #include "grx_generic.h"
 #include "grx_tree.h"
@@ -1339,10 +1407,12 @@ GRX_DEV void load_episode_sums(KP P, int e, int N, float es[NT]) {
 // with reset and observations: PART 2 parks its partial reward in *rew_part and raises rew_flag, PART 1 adds it,
 // clips, adds the termination term and writes rew_buf.
 // es_pre: the env's running episode sums if the caller loaded them early, else nullptr.
-template <int PART>
+// BASE (the grx_step_kernel_base* entries, PART 0): rew_base, the scaled sum of legged_gym's base terms (base_reward_and_sums), joins
+// the total before the only_positive_rewards clip
+template <int PART, bool BASE = false>
 GRX_DEV void reward_and_sums(KP P, const SideConst& C, const RewIn& in, int lane, int side, int e, int N, bool act,
                              float* s_stat, const float* es_pre, float* rew_part = nullptr, int* rew_flag = nullptr,
-                             const float* a_ll = nullptr, bool keep_sums = false) {   // keep_sums: debug entry, reset reported but not applied
+                             const float* a_ll = nullptr, bool keep_sums = false, float rew_base = 0.f) {   // keep_sums: debug entry, reset reported but not applied
     const int j0 = side * LEG;
     const float dtp = P.sim_dt * (float)P.decimation;
     const bool reset = in.reset != 0.f, time_out = in.time_out != 0.f;
@@ -1506,10 +1576,94 @@ GRX_DEV void reward_and_sums(KP P, const SideConst& C, const RewIn& in, int lane
             flag_wait(rew_flag, 1);
             rew += rew_part[lane];
         }
+        if (BASE) rew += rew_base;
         if (P.only_positive_rewards) rew = fmaxf(rew, 0.f);
         if (P.reward_scale_dt[GRX_REW_TERMINATION] != 0.f) rew += term_rt;
         if (writer) P.rew[e] = rew;
     }
+}
+
+// ---- legged_gym's base reward terms (grx_base_reward_term, legged_robot.py:1277-1376) for one lane of the one-wave layout: the scaled
+// terms' sum (returned: reward_and_sums<0, true> adds it before the clip), their episode sums, the debug table and the block's column of
+// the finished episodes' statistics (base_stat_partial; the block is one wave, so lane 0 stores it straight away, every launch).
+// base_z: mean(root_z - measured_heights) of THIS step's scan (legged_robot.py:329-330 precede compute_reward; 0 heights without a scan).
+GRX_DEV float base_reward_and_sums(KP P, const SideConst& C, const RewIn& in, float base_z, int lane, int side, int e, int N, bool act, int grp, bool keep_sums) {
+    const float dtp = P.sim_dt * (float)P.decimation;
+    float sar = 0.f, sacc = 0.f, svel = 0.f, stor = 0.f, slp = 0.f, slv = 0.f, slt = 0.f;
+#pragma unroll
+    for (int k = 0; k < LEG; ++k) {
+        const float da = in.a_last[k] - in.a_cur[k];
+        sar += da * da;
+        const float acc = (in.qd[k] - in.qd_last[k]) / dtp;
+        sacc += acc * acc;
+        svel += in.qd[k] * in.qd[k];
+        stor += in.torque[k] * in.torque[k];
+        float op = 0.f;   // soft position limits, one-sided, not squared (the sum behind limits_dof_pos)
+        if (in.q[k] - C.body[k].slo < 0.f) op += -(in.q[k] - C.body[k].slo);
+        if (in.q[k] - C.body[k].shi > 0.f) op += (in.q[k] - C.body[k].shi);
+        slp += op;
+        slv += fminf(fmaxf(fabsf(in.qd[k]) - C.body[k].vlim * P.soft_dof_vel_limit, 0.f), 1.f);
+        slt += fmaxf(fabsf(in.torque[k]) - C.body[k].effort * P.soft_torque_limit, 0.f);
+    }
+    const V3 F = in.foot_force;   // net foot force of the last sub-step (this lane's foot)
+    const float fnorm = sqrtf(F.x * F.x + F.y * F.y + F.z * F.z);
+    float fcf = fmaxf(fnorm - P.max_contact_force, 0.f);
+    float stum = sqrtf(F.x * F.x + F.y * F.y) > 5.f * fabsf(F.z) ? 1.f : 0.f;   // (the literal 5 of legged_robot.py:1367)
+    sar = pair_sum(sar); sacc = pair_sum(sacc); svel = pair_sum(svel); stor = pair_sum(stor);
+    slp = pair_sum(slp); slv = pair_sum(slv); slt = pair_sum(slt); fcf = pair_sum(fcf); stum = pair_sum(stum);
+    float r[NB];
+    r[GRX_BREW_ACTION_RATE] = sar;
+    r[GRX_BREW_ANG_VEL_XY] = in.bav.x * in.bav.x + in.bav.y * in.bav.y;
+    const float dh = base_z - P.base_height_target;
+    r[GRX_BREW_BASE_HEIGHT] = dh * dh;
+    r[GRX_BREW_DOF_ACC] = sacc;
+    r[GRX_BREW_DOF_POS_LIMITS] = slp;
+    r[GRX_BREW_DOF_VEL] = svel;
+    r[GRX_BREW_DOF_VEL_LIMITS] = slv;
+    r[GRX_BREW_FEET_CONTACT_FORCES] = fcf;
+    r[GRX_BREW_LIN_VEL_Z] = in.blv.z * in.blv.z;
+    r[GRX_BREW_ORIENTATION] = in.pg.x * in.pg.x + in.pg.y * in.pg.y;
+    r[GRX_BREW_STUMBLE] = stum > 0.f ? 1.f : 0.f;
+    r[GRX_BREW_TORQUE_LIMITS] = slt;
+    r[GRX_BREW_TORQUES] = stor;
+    const float ea = in.cmd[2] - in.bav.z;
+    r[GRX_BREW_TRACKING_ANG_VEL] = expf(-(ea * ea) / P.tracking_sigma);
+    const float ex = in.cmd[0] - in.blv.x, ey = in.cmd[1] - in.blv.y;
+    r[GRX_BREW_TRACKING_LIN_VEL] = expf(-(ex * ex + ey * ey) / P.tracking_sigma);
+    float rew = 0.f;
+    // the scales one per lane (lane t holds term t's) and the active set as one scalar mask: 15 scales held in scalar registers pushed the
+    // plane / trimesh heads over the SGPR budget into scratch
+    const uint32_t active = P.base_active;
+    const float scale_v = P.base_scale_dt[lane < NB ? lane : 0];
+#pragma unroll
+    for (int t = 0; t < NB; ++t) {
+        r[t] = ((active >> t) & 1u) ? r[t] * __int_as_float(__builtin_amdgcn_readlane(__float_as_int(scale_v), t)) : 0.f;
+        rew += r[t];
+    }
+    const bool reset = in.reset != 0.f;
+    const bool writer = act && side == 0 && lane_half(lane) == 0;
+    const unsigned long long reset_mask = __ballot(reset && writer);
+    float* const col = P.base_stat_partial + grp;   // (stored term by term: nothing of the statistics stays live)
+#pragma unroll
+    for (int t = 0; t < NB; ++t) {
+        float acc = 0.f;
+        if ((active >> t) & 1u) {   // uniform
+            const float es = P.base_episode_sums[(size_t)t * N + e] + r[t];
+            unsigned long long m = reset_mask;
+            while (m) {
+                const int L = __ffsll((long long)m) - 1;
+                m &= m - 1;
+                acc += __shfl(es, L);
+            }
+            if (writer) {
+                P.base_episode_sums[(size_t)t * N + e] = (reset && !keep_sums) ? 0.f : es;
+                if (P.publish_debug) P.base_reward_terms[(size_t)t * N + e] = r[t];
+            }
+        }
+        if (lane == 0) col[(size_t)t * P.stat_stride] = acc;
+    }
+    if (lane == 0) col[(size_t)NB * P.stat_stride] = (float)__popcll(reset_mask);
+    return rew;
 }
 
 // Eight waves: feet_height = foot z - mean of the measured heights, formed by whoever needs it once the six scanning waves have counted in (FL_SCAN)
@@ -1545,6 +1699,22 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(W > 4 ? 
 // mesh_type 'trimesh': the same step against the reference's slope-corrected triangle mesh (terrain_eval's planes per triangle half, wall_contact)
 template <int W, bool DBG = false>
 __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(W > 4 ? 2 : GRX_WPE, W > 4 ? 2 : GRX_WPE))) void grx_step_kernel_trimesh(GRX_STEP_KERNEL_ARGS) {
+    constexpr int HF = GRX_HF_TRIMESH;
+#include "grx_step_kernel_body.inc"
+}
+
+// ABI 7: the one-wave layout with legged_gym's base reward terms (base_reward_and_sums) -- entries of their own, so that the registered tasks'
+// kernels keep their names and code
+template <bool HF, bool DBG = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GRX_WPE, GRX_WPE))) void grx_step_kernel_base(GRX_STEP_KERNEL_ARGS) {
+    constexpr int W = 1;
+    constexpr bool kBaseTerms = true;
+#include "grx_step_kernel_body.inc"
+}
+template <bool DBG = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GRX_WPE, GRX_WPE))) void grx_step_kernel_base_trimesh(GRX_STEP_KERNEL_ARGS) {
+    constexpr int W = 1;
+    constexpr bool kBaseTerms = true;
     constexpr int HF = GRX_HF_TRIMESH;
 #include "grx_step_kernel_body.inc"
 }
@@ -1879,12 +2049,27 @@ extern "C" void grx_launch_step_debug(const KParams* dP, int N, int heightfield,
 #undef GRX_LAUNCH_DBG
 #undef GRX_LAUNCH_DBG_TM
 }
+// ABI 7: the one-wave entries with legged_gym's base reward terms (heightfield: 0 plane, 1 raster, 2 trimesh)
+extern "C" void grx_launch_step_base(const KParams* dP, int N, int heightfield, const float* actions, float delay, long long common_step,
+                                     const float* noise, float* obs_out, float* pri_out, const StepSeq* sq, hipStream_t stream) {
+    const int nblocks = (N + EPB - 1) / EPB;
+    if (heightfield == 1) hipLaunchKernelGGL((grx_step_kernel_base<true>), dim3(nblocks), dim3(64), 0, stream, dP, actions, delay, common_step, noise, (const float*)nullptr, obs_out, pri_out, *sq);
+    else if (heightfield == 0) hipLaunchKernelGGL((grx_step_kernel_base<false>), dim3(nblocks), dim3(64), 0, stream, dP, actions, delay, common_step, noise, (const float*)nullptr, obs_out, pri_out, *sq);
+    else hipLaunchKernelGGL((grx_step_kernel_base_trimesh<>), dim3(nblocks), dim3(64), 0, stream, dP, actions, delay, common_step, noise, (const float*)nullptr, obs_out, pri_out, *sq);
+}
+extern "C" void grx_launch_step_debug_base(const KParams* dP, int N, int heightfield, const float* actions, long long common_step, const float* noise,
+                                           const float* dbg, const StepSeq* sq, hipStream_t stream) {
+    const int nblocks = (N + EPB - 1) / EPB;
+    if (heightfield == 1) hipLaunchKernelGGL((grx_step_kernel_base<true, true>), dim3(nblocks), dim3(64), 0, stream, dP, actions, 0.f, common_step, noise, dbg, (float*)nullptr, (float*)nullptr, *sq);
+    else if (heightfield == 0) hipLaunchKernelGGL((grx_step_kernel_base<false, true>), dim3(nblocks), dim3(64), 0, stream, dP, actions, 0.f, common_step, noise, dbg, (float*)nullptr, (float*)nullptr, *sq);
+    else hipLaunchKernelGGL((grx_step_kernel_base_trimesh<true>), dim3(nblocks), dim3(64), 0, stream, dP, actions, 0.f, common_step, noise, dbg, (float*)nullptr, (float*)nullptr, *sq);
+}
 extern "C" int grx_debug_rows(void) { return DBG_ROWS; }
 extern "C" int grx_debug_row_of(int what) { return what == 0 ? (int)DBG_TORQUES : what == 1 ? (int)DBG_LAST_LAST_ACTIONS : what == 2 ? (int)DBG_TERM_CONTACT : (int)DBG_APPLY_RESET; }
 // epb: envs per block (= threads per block, at most 64); lds_bytes > 0: the per-body workspace lives in (dynamic) LDS
 extern "C" int grx_launch_step_generic(const KParams* dP, const void* tables, float* ws, int N, int epb, int lds_bytes, int heightfield,
                                        const float* actions, float delay, long long common_step, const float* noise, float* obs_out, float* pri_out,
-                                       long long seq, hipStream_t stream) {
+                                       long long seq, int base, hipStream_t stream) {   // base: the grx_step_generic_base* entries (ABI 7)
     const int nblocks = (N + epb - 1) / epb;
     const GenTables* T = static_cast<const GenTables*>(tables);
     if (lds_bytes > 0) {
@@ -1893,9 +2078,18 @@ extern "C" int grx_launch_step_generic(const KParams* dP, const void* tables, fl
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_generic<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_generic<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_generic_trimesh), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_generic_base<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_generic_base<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_generic_base_trimesh), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
             raised = true;
         }
         ws = nullptr;
+    }
+    if (base) {
+        if (heightfield == 2) hipLaunchKernelGGL(grx_step_generic_base_trimesh, dim3(nblocks), dim3(epb), lds_bytes, stream, dP, T, ws, actions, delay, common_step, noise, obs_out, pri_out, seq);
+        else if (heightfield) hipLaunchKernelGGL(grx_step_generic_base<true>, dim3(nblocks), dim3(epb), lds_bytes, stream, dP, T, ws, actions, delay, common_step, noise, obs_out, pri_out, seq);
+        else hipLaunchKernelGGL(grx_step_generic_base<false>, dim3(nblocks), dim3(epb), lds_bytes, stream, dP, T, ws, actions, delay, common_step, noise, obs_out, pri_out, seq);
+        return 0;
     }
     if (heightfield == 2) hipLaunchKernelGGL(grx_step_generic_trimesh, dim3(nblocks), dim3(epb), lds_bytes, stream, dP, T, ws, actions, delay, common_step, noise, obs_out, pri_out, seq);
     else if (heightfield) hipLaunchKernelGGL(grx_step_generic<true>, dim3(nblocks), dim3(epb), lds_bytes, stream, dP, T, ws, actions, delay, common_step, noise, obs_out, pri_out, seq);
@@ -1915,9 +2109,12 @@ extern "C" void grx_launch_reset_all_generic(const KParams* dP, const void* tabl
 extern "C" int GRX_TREE_FN(grx_tree_lds_bytes)(int nb, int nlc, int nchain, int nsph, int waves) { return (int)sizeof(TreeTab) + waves * 2 * tree_half_words(tree_offsets(nb, nlc, nchain, nsph).total) * 4; }
 extern "C" int GRX_TREE_FN(grx_tree_envs_per_wave)(void) { return TEPW; }
 extern "C" int GRX_TREE_FN(grx_launch_step_tree)(const KParams* dP, const void* tree_tab, const void* gen_tab, int N, int waves, int lds_bytes, int heightfield, const float* actions, float delay,
-                                    long long common_step, const float* noise, float* obs_out, float* pri_out, const StepSeq* sq, hipStream_t stream) {
+                                    long long common_step, const float* noise, float* obs_out, float* pri_out, const StepSeq* sq, int base, hipStream_t stream) {
     static bool raised = false;
     if (!raised) {   // > 64 KB of dynamic LDS needs the opt-in
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_tree_base<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_tree_base<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_tree_base_trimesh<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_tree<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_tree<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_tree_trimesh<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
@@ -1926,6 +2123,12 @@ extern "C" int GRX_TREE_FN(grx_launch_step_tree)(const KParams* dP, const void* 
     const int nblocks = (N + TEPW * waves - 1) / (TEPW * waves);
     const TreeTab* Tt = static_cast<const TreeTab*>(tree_tab);
     const GenTables* Tg = static_cast<const GenTables*>(gen_tab);
+    if (base) {   // ABI 7: the grx_step_tree_base* entries
+        if (heightfield == 2) hipLaunchKernelGGL((grx_step_tree_base_trimesh<false>), dim3(nblocks), dim3(64 * waves), lds_bytes, stream, dP, Tt, Tg, actions, delay, common_step, noise, obs_out, pri_out, *sq, (const float*)nullptr);
+        else if (heightfield) hipLaunchKernelGGL((grx_step_tree_base<true, false>), dim3(nblocks), dim3(64 * waves), lds_bytes, stream, dP, Tt, Tg, actions, delay, common_step, noise, obs_out, pri_out, *sq, (const float*)nullptr);
+        else hipLaunchKernelGGL((grx_step_tree_base<false, false>), dim3(nblocks), dim3(64 * waves), lds_bytes, stream, dP, Tt, Tg, actions, delay, common_step, noise, obs_out, pri_out, *sq, (const float*)nullptr);
+        return 0;
+    }
     if (heightfield == 2) hipLaunchKernelGGL((grx_step_tree_trimesh<false>), dim3(nblocks), dim3(64 * waves), lds_bytes, stream, dP, Tt, Tg, actions, delay, common_step, noise, obs_out, pri_out, *sq, (const float*)nullptr);
     else if (heightfield) hipLaunchKernelGGL((grx_step_tree<true, false>), dim3(nblocks), dim3(64 * waves), lds_bytes, stream, dP, Tt, Tg, actions, delay, common_step, noise, obs_out, pri_out, *sq, (const float*)nullptr);
     else hipLaunchKernelGGL((grx_step_tree<false, false>), dim3(nblocks), dim3(64 * waves), lds_bytes, stream, dP, Tt, Tg, actions, delay, common_step, noise, obs_out, pri_out, *sq, (const float*)nullptr);
@@ -1933,9 +2136,12 @@ extern "C" int GRX_TREE_FN(grx_launch_step_tree)(const KParams* dP, const void* 
 }
 // TEST-ONLY (grx_debug_post_physics): the post-physics half of the tree kernel on injected state (a 10-dof model forced through it)
 extern "C" int GRX_TREE_FN(grx_launch_step_tree_debug)(const KParams* dP, const void* tree_tab, const void* gen_tab, int N, int waves, int lds_bytes, int heightfield, const float* actions,
-                                          long long common_step, const float* noise, const float* dbg, const StepSeq* sq, hipStream_t stream) {
+                                          long long common_step, const float* noise, const float* dbg, const StepSeq* sq, int base, hipStream_t stream) {
     static bool raised = false;
     if (!raised) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_tree_base<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_tree_base<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_tree_base_trimesh<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_tree<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_tree<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_tree_trimesh<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
@@ -1944,6 +2150,12 @@ extern "C" int GRX_TREE_FN(grx_launch_step_tree_debug)(const KParams* dP, const 
     const int nblocks = (N + TEPW * waves - 1) / (TEPW * waves);
     const TreeTab* Tt = static_cast<const TreeTab*>(tree_tab);
     const GenTables* Tg = static_cast<const GenTables*>(gen_tab);
+    if (base) {
+        if (heightfield == 2) hipLaunchKernelGGL((grx_step_tree_base_trimesh<true>), dim3(nblocks), dim3(64 * waves), lds_bytes, stream, dP, Tt, Tg, actions, 0.f, common_step, noise, (float*)nullptr, (float*)nullptr, *sq, dbg);
+        else if (heightfield) hipLaunchKernelGGL((grx_step_tree_base<true, true>), dim3(nblocks), dim3(64 * waves), lds_bytes, stream, dP, Tt, Tg, actions, 0.f, common_step, noise, (float*)nullptr, (float*)nullptr, *sq, dbg);
+        else hipLaunchKernelGGL((grx_step_tree_base<false, true>), dim3(nblocks), dim3(64 * waves), lds_bytes, stream, dP, Tt, Tg, actions, 0.f, common_step, noise, (float*)nullptr, (float*)nullptr, *sq, dbg);
+        return 0;
+    }
     if (heightfield == 2) hipLaunchKernelGGL((grx_step_tree_trimesh<true>), dim3(nblocks), dim3(64 * waves), lds_bytes, stream, dP, Tt, Tg, actions, 0.f, common_step, noise, (float*)nullptr, (float*)nullptr, *sq, dbg);
     else if (heightfield) hipLaunchKernelGGL((grx_step_tree<true, true>), dim3(nblocks), dim3(64 * waves), lds_bytes, stream, dP, Tt, Tg, actions, 0.f, common_step, noise, (float*)nullptr, (float*)nullptr, *sq, dbg);
     else hipLaunchKernelGGL((grx_step_tree<false, true>), dim3(nblocks), dim3(64 * waves), lds_bytes, stream, dP, Tt, Tg, actions, 0.f, common_step, noise, (float*)nullptr, (float*)nullptr, *sq, dbg);
@@ -1973,5 +2185,102 @@ extern "C" void grx_launch_set_state(const KParams* dP, int N, const float* root
     hipLaunchKernelGGL(grx_set_state_kernel, dim3((cnt + 255) / 256), dim3(256), 0, stream, dP, root, q, qd, env_ids, n);
 }
 extern "C" int grx_envs_per_block(void) { return EPB; }
+// ABI 7, handles with base reward terms: the finished episodes' base sums of a reset outside a step (grx_reset_all / grx_reset_idx; mask as
+// there, read BEFORE grx_reset_all_kernel consumes it): one env per lane, a column of base_stat_partial per 64-env block, sums zeroed
+__global__ __launch_bounds__(64) void grx_base_reset_kernel(const KParams* __restrict__ Pg, const uint8_t* __restrict__ mask) {
+    KP P = GRX_PARAMS(Pg);
+    const int N = P.N, lane = threadIdx.x;
+    const int e = blockIdx.x * 64 + lane;
+    const bool sel = e < N && (!mask || mask[e] != 0);
+    float* col = P.base_stat_partial + blockIdx.x;
+    for (int t = 0; t < NB; ++t) {
+        float v = 0.f;
+        if (sel) { v = P.base_episode_sums[(size_t)t * N + e]; P.base_episode_sums[(size_t)t * N + e] = 0.f; }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+        if (lane == 0) col[(size_t)t * P.stat_stride] = v;
+    }
+    const unsigned long long m = __ballot(sel);
+    if (lane == 0) col[(size_t)NB * P.stat_stride] = (float)__popcll(m);
+}
+// ... and its reduction, behind every launch of such a handle that finishes episodes (step, debug step, reset): one block, a wave per base term,
+// the nb columns of the launch just enqueued (stream order: no fence); the means (legged_robot.py:420-424) into base_stats -- kept when nobody
+// reset, as stat_publish does -- and row seq of the history ring
+__global__ __launch_bounds__(64 * NB) void grx_base_stats_kernel(const KParams* __restrict__ Pg, long long seq, int nb) {
+    KP P = GRX_PARAMS(Pg);
+    const int t = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const float* crow = P.base_stat_partial + (size_t)NB * P.stat_stride;
+    const float* row = P.base_stat_partial + (size_t)t * P.stat_stride;
+    float cnt = 0.f, s = 0.f;
+    for (int b = lane; b < nb; b += 64) { cnt += crow[b]; s += row[b]; }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) { cnt += __shfl_xor(cnt, off); s += __shfl_xor(s, off); }
+    if (lane == 0) {
+        float v = P.base_stats[t];
+        if (cnt > 0.f) { v = s / cnt / P.max_episode_length_s; P.base_stats[t] = v; }
+        P.base_stat_hist[(size_t)(seq & (GRX_STATS_HISTORY - 1)) * NB + t] = v;
+    }
+}
+// cfg.commands.curriculum (legged_robot.py:395-396, 828-838), behind a step of a handle that has it: ONE block (no grid-wide wait).  The step's
+// resets left their tracking_lin_vel episode sums (this step's reward included) in base_stat_partial; if their mean per step exceeds
+// 0.8 x scale x dt, lin_vel_x widens by 0.5 either way -- in the device copy of the launch parameters, which every later kernel reads -- and
+// the reset envs' commands are redrawn from the new range with the step's own counter-based uniforms (reset_rand's GRX_RNG_CMD_RESET block:
+// the draws the step made), the |cmd_xy| > 0.1 zeroing included; their observation and privileged-observation columns 0, 1 follow.  The
+// step's time-based resamples came before the check and keep the old range (legged_robot.py:316-317).  Nothing reset: no work.
+constexpr int kCurriculumThreads = 1024;
+// (the range is read and written through the same plain pointer Pw: the one field this kernel changes is not read through the
+// constant-address-space view P, whose other fields stay unchanged during the launch)
+__global__ __launch_bounds__(kCurriculumThreads) void grx_curriculum_kernel(const KParams* Pg, KParams* Pw, int nb, uint32_t step,
+                                                                            float* __restrict__ obs, int nobs, float* __restrict__ pri, int npri) {
+    KP P = GRX_PARAMS(Pg);
+    __shared__ float s_red[2][kCurriculumThreads / 64];
+    __shared__ float s_rng[2];
+    __shared__ int s_widen;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const float* crow = P.base_stat_partial + (size_t)NB * P.stat_stride;
+    const float* row = P.base_stat_partial + (size_t)GRX_BREW_TRACKING_LIN_VEL * P.stat_stride;
+    float cnt = 0.f, s = 0.f;
+    for (int b = tid; b < nb; b += kCurriculumThreads) { cnt += crow[b]; s += row[b]; }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) { cnt += __shfl_xor(cnt, off); s += __shfl_xor(s, off); }
+    if (lane == 0) { s_red[0][w] = cnt; s_red[1][w] = s; }
+    __syncthreads();
+    if (tid == 0) {
+        float c = 0.f, t = 0.f;
+        for (int i = 0; i < kCurriculumThreads / 64; ++i) { c += s_red[0][i]; t += s_red[1][i]; }
+        const float lo = Pw->cmd_lin_vel_x[0], hi = Pw->cmd_lin_vel_x[1];
+        const bool widen = c > 0.f && t / c / P.max_episode_length > 0.8f * P.base_scale_dt[GRX_BREW_TRACKING_LIN_VEL];
+        s_rng[0] = widen ? fminf(fmaxf(lo - 0.5f, -P.max_curriculum), 0.f) : lo;
+        s_rng[1] = widen ? fminf(fmaxf(hi + 0.5f, 0.f), P.max_curriculum) : hi;
+        s_widen = widen && (s_rng[0] != lo || s_rng[1] != hi);
+    }
+    __syncthreads();
+    if (!s_widen) return;   // (uniform)
+    const float lo = s_rng[0], hi = s_rng[1];
+    const int N = P.N;
+    const uint32_t k0 = (uint32_t)P.seed, k1 = (uint32_t)(P.seed >> 32);
+    const float clipo = P.clip_observations;
+    for (int e = tid; e < N; e += kCurriculumThreads) {
+        if (!P.reset[e]) continue;
+        const U4 a = grx_philox4x32_10((uint32_t)(P.env_offset + e), step, GRX_RNG_CMD_RESET, 0u, k0, k1);   // = reset_rand(...).cmd
+        const float c0 = lerp_u(grx_u01(a.x), lo, hi);
+        const float c1 = lerp_u(grx_u01(a.y), P.cmd_lin_vel_y[0], P.cmd_lin_vel_y[1]);
+        const float keep = sqrtf(c0 * c0 + c1 * c1) > 0.1f ? 1.0f : 0.0f;
+        const float x = c0 * keep, y = c1 * keep;
+        P.commands[e] = x; P.commands[(size_t)N + e] = y;
+        obs[(size_t)e * nobs + 0] = fminf(fmaxf(x, -clipo), clipo); obs[(size_t)e * nobs + 1] = fminf(fmaxf(y, -clipo), clipo);
+        pri[(size_t)e * npri + 0] = fminf(fmaxf(x, -clipo), clipo); pri[(size_t)e * npri + 1] = fminf(fmaxf(y, -clipo), clipo);
+    }
+    if (tid == 0) { Pw->cmd_lin_vel_x[0] = lo; Pw->cmd_lin_vel_x[1] = hi; }   // (thread 0 read the old range through Pw before the barrier)
+}
+extern "C" void grx_launch_curriculum(const KParams* dP, int nb, uint32_t step, float* obs, int nobs, float* pri, int npri, hipStream_t stream) {
+    hipLaunchKernelGGL(grx_curriculum_kernel, dim3(1), dim3(kCurriculumThreads), 0, stream, dP, const_cast<KParams*>(dP), nb, step, obs, nobs, pri, npri);
+}
+extern "C" void grx_launch_base_reset(const KParams* dP, int N, const uint8_t* mask, hipStream_t stream) {
+    hipLaunchKernelGGL(grx_base_reset_kernel, dim3((N + 63) / 64), dim3(64), 0, stream, dP, mask);
+}
+extern "C" void grx_launch_base_stats(const KParams* dP, long long seq, int nb, hipStream_t stream) {
+    hipLaunchKernelGGL(grx_base_stats_kernel, dim3(1), dim3(64 * NB), 0, stream, dP, seq, nb);
+}
 #endif   // !GRX_TREE16_TU
 #endif   // GRX_QUAD_TU

@@ -251,10 +251,11 @@
         if (t != GRX_REW_TERMINATION && sc_t != 0.f) { rt = r[t] * sc_t; rew += rt; }
         r[t] = rt;
     }
-    if (P.only_positive_rewards) rew = fmaxf(rew, 0.f);
+    if (!kBaseTerms && P.only_positive_rewards) rew = fmaxf(rew, 0.f);   // (grx_step_generic_base*: after the base terms, below)
+    float rew_term = 0.f;
     if (P.reward_scale_dt[GRX_REW_TERMINATION] != 0.f) {
         const float rt = r[GRX_REW_TERMINATION] = ((reset && !time_out) ? 1.f : 0.f) * P.reward_scale_dt[GRX_REW_TERMINATION];
-        rew += rt;
+        if (kBaseTerms) rew_term = rt; else rew += rt;
     }
     // episode sums; finished episodes -> the block's statistics row (deterministic lane order)
     const unsigned long long reset_mask = __ballot(reset && act);
@@ -272,6 +273,18 @@
         }
     }
     if (lane == 0) s_stat[NT] = (float)__popcll(reset_mask);
+    if constexpr (kBaseTerms) {   // (grx_step_generic_base*: legged_gym's base terms, DESIGN.md 4.5; one env per lane, the block is one wave) -- then the
+        BaseJ bj;                 // total of both tables is clipped and the termination term added
+        for (int j = 0; j < nd; ++j)
+            base_joint(P, bj, a_last[(size_t)j * N], a_cur[(size_t)j * N], q[(size_t)j * N], qd[(size_t)j * N], qd_last[(size_t)j * N], tau[(size_t)j * N],
+                       T.slo[j], T.shi[j], T.vlim[j], T.effort[j], dtp);
+        float rb[NB];
+        const float base_z = nh > 0 ? B.pos.z - hsum / (float)nh : B.pos.z;   // mean(root_z - measured_heights), this step's scan
+        rew += base_env_terms(P, bj, foot_force[0], foot_force[1], blv, bav, pg, ea.cmd, base_z, lane, rb);
+        base_env_store(P, rb, e, (int)N, reset, reset, act, lane, blockIdx.x);
+        if (P.only_positive_rewards) rew = fmaxf(rew, 0.f);
+        rew += rew_term;
+    }
     // ---- reset_idx (masked, in-kernel)
     if (reset) {
         gen_reset_env(P, T, genv, step, true, B, ea, q, qd, N, e);

@@ -1,6 +1,7 @@
 // grx_step_kernel_body.inc -- the BODY of the fused step kernel, included between the braces of its two __global__ heads in grx_kernels.hip:
 //   grx_step_kernel<HF, W, DBG>(GRX_STEP_KERNEL_ARGS)        plane (HF = false) / the raster as a heightfield (HF = true)
 //   grx_step_kernel_trimesh<W, DBG>(GRX_STEP_KERNEL_ARGS)    mesh_type 'trimesh': `constexpr int HF = GRX_HF_TRIMESH` precedes the include
+//   grx_step_kernel_base<HF, DBG>, grx_step_kernel_base_trimesh<DBG>   W = 1 with legged_gym's base reward terms (`constexpr bool kBaseTerms = true`)
 // (the terrain is a compile-time property of everything below; a third value of a template parameter would have changed the heightfield kernels' names,
 //  a device-function body under two wrappers their register allocation: DESIGN.md 3, profiles/r06_experiments.md)
     static_assert(!DBG || W == 1 || W == 4 || W == 8, "the debug injection path exists for the one-wave layout and the pipelines");
@@ -587,6 +588,10 @@
             int i = 0;
             rewin_fields(rin, [&](float& x) { s_rw[(i++) * 64 + lane] = x; });
             flag_set(s_flag + FL_REW, 1, lane);
+        } else if constexpr (kBaseTerms) {   // (grx_step_kernel_base*: legged_gym's base terms join the total before the clip)
+            const float base_z = nh > 0 ? st.pos.z - hsum / (float)nh : st.pos.z;   // mean(root_z - measured_heights), this step's scan
+            const float rb = base_reward_and_sums(P, C, rin, base_z, lane, side, e, N, act, grp, DBG && !dbg_apply_reset);
+            reward_and_sums<0, true>(P, C, rin, lane, side, e, N, act, s_stat, es_early, nullptr, nullptr, DBG ? a_ll : nullptr, DBG && !dbg_apply_reset, rb);
         } else reward_and_sums<0>(P, C, rin, lane, side, e, N, act, s_stat, es_early, nullptr, nullptr, DBG ? a_ll : nullptr, DBG && !dbg_apply_reset);
     }
     const bool writer = act0 && side == 0;

@@ -480,10 +480,11 @@
         if (t != GRX_REW_TERMINATION && ((term_on >> t) & 1ull)) { rt = r[t] * sc_t; rew += rt; }
         r[t] = rt;
     }
-    if (P.only_positive_rewards) rew = fmaxf(rew, 0.f);
+    if (!kBaseTerms && P.only_positive_rewards) rew = fmaxf(rew, 0.f);   // (grx_step_tree_base*: after the base terms, below)
+    float rew_term = 0.f;
     if ((term_on >> GRX_REW_TERMINATION) & 1ull) {
         const float rt = r[GRX_REW_TERMINATION] = ((reset && !time_out) ? 1.f : 0.f) * scale_of(GRX_REW_TERMINATION);
-        rew += rt;
+        if (kBaseTerms) rew_term = rt; else rew += rt;
     }
     // episode sums (the group's first lane); finished episodes -> the block's statistics row (deterministic lane order)
 #ifdef GRX_PROFILE_SECTIONS
@@ -509,6 +510,22 @@
         }
     }
     if (lane == 0) s_stat[wave][NT] = (float)__popcll(reset_mask);
+    if constexpr (kBaseTerms) {   // (grx_step_tree_base*: legged_gym's base terms, DESIGN.md 4.5 -- here, where the 36 terms' arrays are dead) a lane
+        BaseJ bj;                 // sums its joints, the group adds up; then the total of both tables is clipped and the termination term added
+        for (int j = c; j < nd; j += TG) {
+            const TreeDof& td = T.dof[j];
+            base_joint(P, bj, TW(o.dof + TD_ALAST * GRX_MAX_DOFS + j), TW(o.dof + TD_ACUR * GRX_MAX_DOFS + j), TW(TBO(j + 1) + T_QPUB),
+                       TW(TBO(j + 1) + T_QDPUB), P.last_dof_vel[(size_t)j * N + e], TW(TBO(j + 1) + T_TAU), td.slo, td.shi, td.vlim, td.effort, dtp);
+        }
+        bj.ar = grp_sum(bj.ar); bj.acc = grp_sum(bj.acc); bj.vel = grp_sum(bj.vel); bj.tor = grp_sum(bj.tor);
+        bj.plim = grp_sum(bj.plim); bj.vlim = grp_sum(bj.vlim); bj.tlim = grp_sum(bj.tlim);
+        float rb[NB];
+        const float base_z = nh > 0 ? B.pos.z - hsum / (float)nh : B.pos.z;   // mean(root_z - measured_heights), this step's scan
+        rew += base_env_terms(P, bj, foot_force[0], foot_force[1], blv, bav, pg, ea.cmd, base_z, lane, rb);
+        base_env_store(P, rb, e, (int)N, reset, reset && dbg_apply_reset, actl, lane, grp * nwaves + wave);
+        if (P.only_positive_rewards) rew = fmaxf(rew, 0.f);
+        rew += rew_term;
+    }
 #ifdef GRX_PROFILE_SECTIONS
     if (threadIdx.x == 0 && blockIdx.x < 64) P.prof[(size_t)blockIdx.x * GRX_PROF_SLOTS + 12] = clock64() - tt_begin;
 #endif

@@ -656,5 +656,17 @@ __global__ __launch_bounds__(64 * TWAVES_MAX) __attribute__((amdgpu_waves_per_eu
     constexpr int HF = GRX_HF_TRIMESH;
 #include "grx_step_tree_body.inc"
 }
+// ABI 7: the same with legged_gym's base reward terms -- entries of their own, the kernels above keep their names and code
+template <bool HF, bool DBG = false>
+__global__ __launch_bounds__(64 * TWAVES_MAX) __attribute__((amdgpu_waves_per_eu(1, 1))) void grx_step_tree_base(GRX_STEP_TREE_ARGS) {
+    constexpr bool kBaseTerms = true;
+#include "grx_step_tree_body.inc"
+}
+template <bool DBG = false>
+__global__ __launch_bounds__(64 * TWAVES_MAX) __attribute__((amdgpu_waves_per_eu(1, 1))) void grx_step_tree_base_trimesh(GRX_STEP_TREE_ARGS) {
+    constexpr bool kBaseTerms = true;
+    constexpr int HF = GRX_HF_TRIMESH;
+#include "grx_step_tree_body.inc"
+}
 #undef TW
 #undef TBO

@@ -8,4 +8,6 @@
 #define GRX_TREE_GDEV 16
 #define grx_step_tree grx_step_tree16   // (a name of its own in the profiles)
 #define grx_step_tree_trimesh grx_step_tree16_trimesh
+#define grx_step_tree_base grx_step_tree16_base
+#define grx_step_tree_base_trimesh grx_step_tree16_base_trimesh
 #include "grx_kernels.hip"

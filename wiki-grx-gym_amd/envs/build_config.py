@@ -102,6 +102,8 @@ def build(cfg, sim_dt, num_envs, env_offset=0, total_envs=None, seed=1, terrain=
     r = cfg.commands.ranges
     _set(c.cmd_lin_vel_x, r.lin_vel_x); _set(c.cmd_lin_vel_y, r.lin_vel_y); _set(c.cmd_ang_vel_yaw, r.ang_vel_yaw)
     c.heading_command = int(bool(cfg.commands.heading_command))   # legged_robot.py:320-326 (GRx tasks: False, gr1t1_config.py:151)
+    c.command_curriculum = int(bool(getattr(cfg.commands, "curriculum", False)))   # legged_robot.py:395-396, 828-838
+    c.max_curriculum = float(getattr(cfg.commands, "max_curriculum", 1.0))
     _set(c.init_pos, cfg.init_state.pos); _set(c.init_rot, cfg.init_state.rot)
     _set(c.init_lin_vel, cfg.init_state.lin_vel); _set(c.init_ang_vel, cfg.init_state.ang_vel)
     dr = cfg.domain_rand
@@ -123,12 +125,19 @@ def build(cfg, sim_dt, num_envs, env_offset=0, total_envs=None, seed=1, terrain=
     # rewards: scale / sigma per term, by name
     rw = cfg.rewards
     scales = {k: v for k, v in vars_of(rw.scales).items()}
-    unknown = [k for k, v in scales.items() if v != 0 and k not in _capi.REWARD_TERMS]
+    unknown = [k for k, v in scales.items() if v != 0 and k not in _capi.REWARD_TERMS and k not in _capi.BASE_REWARD_TERMS]
     if unknown:
         raise ValueError(f"reward terms without an implementation: {unknown}")
     for t, name in enumerate(_capi.REWARD_TERMS):
         c.reward_scale[t] = float(scales.get(name, 0.0))
         c.reward_sigma[t] = float(getattr(rw, "sigma_" + name, 0.0))
+    # legged_gym's base terms (ABI 7, legged_robot.py:1277-1376): a table of their own; any of them active runs the one-wave layout
+    for t, name in enumerate(_capi.BASE_REWARD_TERMS):
+        c.base_reward_scale[t] = float(scales.get(name, 0.0))
+    c.tracking_sigma = float(getattr(rw, "tracking_sigma", 0.25))
+    c.max_contact_force = float(getattr(rw, "max_contact_force", 100.0))
+    if c.command_curriculum and scales.get("tracking_lin_vel", 0.0) == 0:   # (the reference raises KeyError at the first reset: legged_robot.py:836)
+        raise ValueError("commands.curriculum needs the tracking_lin_vel reward term (a non-zero rewards.scales.tracking_lin_vel)")
     c.only_positive_rewards = int(rw.only_positive_rewards)
     c.base_height_target = rw.base_height_target
     c.swing_feet_height_target = getattr(rw, "swing_feet_height_target", 0.1)
@@ -200,7 +209,7 @@ def build(cfg, sim_dt, num_envs, env_offset=0, total_envs=None, seed=1, terrain=
     else:
         raise ValueError(f"Terrain mesh type '{t.mesh_type}' not supported (plane, heightfield, trimesh)")
     meta["dt"] = dt
-    meta["active_terms"] = [nm for nm in _capi.REWARD_TERMS if scales.get(nm, 0.0) != 0]
+    meta["active_terms"] = sorted(nm for nm in _capi.REWARD_TERMS + _capi.BASE_REWARD_TERMS if scales.get(nm, 0.0) != 0)   # both tables, alphabetical
     return c, keep, meta
 
 

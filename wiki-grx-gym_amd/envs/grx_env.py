@@ -52,6 +52,12 @@ class _EpisodeInfo(dict):
         row = env._stats_hist[self._slot]
         for k, i in env._episode_keys.items():
             dict.setdefault(self, k, row[i])   # (a caller's own assignment wins)
+        if env._base_episode_keys:   # legged_gym's base terms: their own history ring, current after every launch
+            brow = env._base_stats_hist[self._slot]
+            for k, i in env._base_episode_keys.items():
+                dict.setdefault(self, k, brow[i])
+        for k, ij in env._curriculum_keys.items():   # the command curriculum's keys (legged_robot.py:430-436): views of the current ranges
+            dict.setdefault(self, k, env._command_ranges_dev[ij])
         self._filled = True
 
     def __setitem__(self, key, value):
@@ -67,7 +73,8 @@ class _EpisodeInfo(dict):
         return dict.get(self, key, default)
 
     def __contains__(self, key):
-        return key in self._env._episode_keys or dict.__contains__(self, key)
+        env = self._env
+        return key in env._episode_keys or key in env._base_episode_keys or key in env._curriculum_keys or dict.__contains__(self, key)
 
     def __iter__(self):
         self._fill()
@@ -125,7 +132,7 @@ class GRxEnv:
         self.dt = cfg.control.decimation * sim_dt
         self.obs_scales = cfg.normalization.obs_scales
         self.reward_scales = class_to_dict(cfg.rewards.scales)
-        self.command_ranges = class_to_dict(cfg.commands.ranges)
+        self._command_ranges_cfg = class_to_dict(cfg.commands.ranges)
         self.max_episode_length_s = cfg.env.episode_length_s
         self.max_episode_length = np.ceil(self.max_episode_length_s / self.dt)
         cfg.domain_rand.push_interval = np.ceil(cfg.domain_rand.push_interval_s / self.dt)
@@ -177,7 +184,9 @@ class GRxEnv:
             else:
                 self.reward_scales[k] *= self.dt
         self.reward_names = [n for n in self.reward_scales if n != "termination"]
-        self._term_index = {n: _capi.REWARD_TERMS.index(n) for n in self.reward_scales}
+        # (the merged, alphabetical set of both tables: the FF/GR1 terms and legged_gym's base terms, ABI 7)
+        self._term_index = {n: _capi.REWARD_TERMS.index(n) for n in self.reward_scales if n in _capi.REWARD_TERMS}
+        self._base_index = {n: _capi.BASE_REWARD_TERMS.index(n) for n in self.reward_scales if n in _capi.BASE_REWARD_TERMS}
         # buffers (base_task.py:69-76, legged_robot.py:106-203): zero-copy views
         t = self._sim.tensor
         # obs_buf / pri_obs_buf are REBOUND to fresh tensors every step, as in the reference (torch.cat / torch.clip
@@ -222,7 +231,16 @@ class GRxEnv:
         self._episode_keys = {"rew_" + n: i for n, i in self._term_index.items()}
         if self.cfg.terrain.curriculum:
             self._episode_keys["terrain_level"] = _capi.NUM_REWARD_TERMS + 1
-        self.episode_sums = {n: self._episode_sums[i] for n, i in self._term_index.items()}
+        self._base_episode_keys = {"rew_" + n: i for n, i in self._base_index.items()}
+        # cfg.commands.curriculum (legged_robot.py:395-396, 828-838): the library widens the ranges on the device (GRX_T_COMMAND_RANGES); the
+        # reference's extras keys, its overwrite of legged_robot.py:431-432 included (max_command_x holds hi, there is no min_command_x)
+        self._command_ranges_dev = t("COMMAND_RANGES") if self.cfg.commands.curriculum else None
+        self._curriculum_keys = {"max_command_x": (0, 1), "min_command_y": (1, 0), "max_command_y": (1, 1), "min_command_yaw": (2, 0),
+                                 "max_command_yaw": (2, 1)} if self._command_ranges_dev is not None else {}
+        self._base_stats_hist = t("BASE_EPISODE_STATS_HISTORY") if self._base_index else None
+        base_sums = t("BASE_EPISODE_SUMS") if self._base_index else None
+        self.episode_sums = {n: (self._episode_sums[self._term_index[n]] if n in self._term_index else base_sums[self._base_index[n]])
+                             for n in self.reward_scales}
         # (N, num_bodies, 3) net contact force per URDF link, last sub-step (LR:117): zero-copy view of the library tensor
         self.contact_forces = t("CONTACT_FORCES")[:, :self.num_bodies]
         self._rbs = None
@@ -292,6 +310,16 @@ class GRxEnv:
         if self.cfg.env.send_timeouts:
             self.extras["time_outs"] = self.time_out_buf
         return self.obs_buf, self.pri_obs_buf, self.rew_buf, self.reset_buf, self.extras
+
+    @property
+    def command_ranges(self):
+        """The reference's dict of [lo, hi] command ranges (legged_robot.py:91-104); with cfg.commands.curriculum the current device ranges
+        the library draws from (reads GRX_T_COMMAND_RANGES: synchronises)."""
+        r = {k: list(v) if isinstance(v, (list, tuple)) else v for k, v in self._command_ranges_cfg.items()}
+        if getattr(self, "_command_ranges_dev", None) is not None:
+            dev = self._command_ranges_dev.cpu().tolist()
+            r["lin_vel_x"], r["lin_vel_y"], r["ang_vel_yaw"] = dev[0], dev[1], dev[2]
+        return r
 
     def reset(self):
         """base_task.py:117-121: reset every env, then one zero-action step."""
