@@ -438,9 +438,9 @@ __global__ __launch_bounds__(TAIL_THR) void tail_apply_kernel(const grx_ppo_tail
         }
         const float total = sqrtf(tot);
         s_clip = fminf(A.max_grad_norm / (total + 1e-6f), 1.0f);
-        if (blockIdx.x == 0 && A.sums) {
-            const float ok = bad ? 0.f : 1.f;
-            A.sums[0] += *A.value_loss * ok; A.sums[1] += *A.surrogate_loss * ok; A.sums[2] = *A.kl;
+        if (blockIdx.x == 0 && A.sums) {   // (a skipped step adds nothing: selected, not multiplied by 0 -- its losses may be NaN)
+            if (!bad) { A.sums[0] += *A.value_loss; A.sums[1] += *A.surrogate_loss; }
+            A.sums[2] = *A.kl;
         }
     }
     __syncthreads();

@@ -316,15 +316,10 @@ class PPO:
             # For these GEMM shapes (batch ~10^4 rows, 39..512 columns, fp32) rocBLAS's kernel choices beat hipBLASLt's by 2x
             # on the weight-gradient products dY^T X (27-48 us against 66-73 us, tools/gpu_gemm_probe.py).  torch's BLAS
             # preference is process-global, so it is switched for the update only (GRX_PPO_BLAS=hipblaslt leaves it alone).
-            prev_blas = torch.backends.cuda.preferred_blas_library()
-            if os.environ.get("GRX_PPO_BLAS", "rocblas") == "rocblas":
-                torch.backends.cuda.preferred_blas_library("cublas")
-            try:
+            with self._blas_for_update():
                 if self._use_graph:
                     return self._update_graphed()
                 return self._update_device()
-            finally:
-                torch.backends.cuda.preferred_blas_library(prev_blas)
         mean_value_loss, mean_surrogate_loss = 0.0, 0.0
         ac, multi = self.actor_critic, _collective_path()
         adaptive = self.desired_kl is not None and self.schedule == "adaptive"
@@ -372,6 +367,17 @@ class PPO:
         self.num_updates = self.num_learning_epochs * self.num_mini_batches
         return mean_value_loss / self.num_updates, mean_surrogate_loss / self.num_updates
 
+    @contextlib.contextmanager
+    def _blas_for_update(self):
+        """torch's BLAS preference for the update: rocBLAS (GRX_PPO_BLAS=hipblaslt: left alone), put back afterwards"""
+        prev_blas = torch.backends.cuda.preferred_blas_library()
+        if os.environ.get("GRX_PPO_BLAS", "rocblas") == "rocblas":
+            torch.backends.cuda.preferred_blas_library("cublas")
+        try:
+            yield
+        finally:
+            torch.backends.cuda.preferred_blas_library(prev_blas)
+
     def _losses(self, obs, cobs, actions, target_values, advantages, returns, old_logp, old_mu, old_sigma):
         """(surrogate_loss, value_loss, loss, kl_mean) of one minibatch -- ppo.py:215-245.
 
@@ -380,7 +386,9 @@ class PPO:
         ac = self.actor_critic
         adaptive = self.desired_kl is not None and self.schedule == "adaptive"
         if self._fused_loss and not ac.fixed_std and ac.num_actor_output <= 32:   # the kernel's action-count limit
-            if self._two_streams:
+            # (only while the actor's GEMMs go to rocBLAS -- update() / _build_graph's preference: with torch's default hipBLASLt on BOTH
+            #  streams, the value head's weight gradient at minibatch 49152 came out wrong once and the step did not finish twice)
+            if self._two_streams and torch.backends.cuda.preferred_blas_library() == torch._C._BlasBackend.Cublas:
                 # actor and critic are independent until the loss: the critic's forward (and, through autograd's stream
                 # bookkeeping, its backward) runs on a second stream
                 cur = torch.cuda.current_stream(self.device)
@@ -452,9 +460,8 @@ class PPO:
             nn.utils.clip_grad_norm_(ac.parameters(), self.max_grad_norm, foreach=True)
             self.optimizer.step()
             with torch.no_grad():
-                ok = (~bad).float()
-                sums[0] += value_loss.detach() * ok
-                sums[1] += surrogate_loss.detach() * ok
+                sums[0] += torch.where(bad, 0.0, value_loss.detach())   # (a skipped step adds nothing, also when its losses are NaN: NaN * 0 is NaN)
+                sums[1] += torch.where(bad, 0.0, surrogate_loss.detach())
                 sums[2] = kl_mean
         self.num_updates = self.num_learning_epochs * self.num_mini_batches
         host = sums.tolist()                           # the only device->host transfer of the update
@@ -484,9 +491,8 @@ class PPO:
         nn.utils.clip_grad_norm_(self.actor_critic.parameters(), self.max_grad_norm, foreach=True)
         self.optimizer.step()
         with torch.no_grad():
-            ok = (~bad).float()
-            sums[0] += value_loss.detach() * ok
-            sums[1] += surrogate_loss.detach() * ok
+            sums[0] += torch.where(bad, 0.0, value_loss.detach())   # (a skipped step adds nothing, also when its losses are NaN: NaN * 0 is NaN)
+            sums[1] += torch.where(bad, 0.0, surrogate_loss.detach())
             sums[2] = kl_mean
 
     def _step_tail(self, loss, kl_mean, value_loss, surrogate_loss, sums, adaptive, bad_flag=None):
@@ -540,9 +546,8 @@ class PPO:
         nn.utils.clip_grad_norm_(self.actor_critic.parameters(), self.max_grad_norm, foreach=True)
         self.optimizer.step()
         with torch.no_grad():
-            ok = (~bad).float()
-            sums[0] += self._mid[0] * ok
-            sums[1] += self._mid[1] * ok
+            sums[0] += torch.where(bad, 0.0, self._mid[0])   # (a skipped step adds nothing, also when its losses are NaN: NaN * 0 is NaN)
+            sums[1] += torch.where(bad, 0.0, self._mid[1])
             sums[2] = kl_mean
 
     def _build_graph(self, mb):
