@@ -109,6 +109,21 @@ int grx_ppo_gather_rows(int n_tensors, const float* const* src, float* const* ds
 
 int grx_mlp_layer(int M, int K, int N, const float* X, const float* W, const float* bias, float* Y, int elu, void* stream);
 
+/* The bf16 matrix path of a hidden layer (PPO(precision="bf16")): the three products of a Linear layer with bf16 operands and fp32
+ * accumulation on v_mfma_f32_32x32x16_bf16.  Operands stay fp32 in memory and are rounded to bf16 (round-to-nearest-even, NaN kept)
+ * as they are loaded; outputs are fp32.  Each output's summation order is fixed by the shape (a row's result does not depend on the
+ * rows beside it), and the weight gradient adds its batch slabs in a fixed order: the results are deterministic.  Contiguous
+ * row-major fp32 everywhere; any size >= 1.  Return 0, or negative for invalid arguments (nothing is launched) / a failed launch.
+ *   grx_mlp_layer_bf16:       Y [M][N] = act(bf16(X [M][K]) . bf16(W [N][K])^T + bias), act = ELU(alpha 1) when `elu` != 0
+ *                             (grx_mlp_layer's signature and epilogue)
+ *   grx_mlp_input_grad_bf16:  dX [M][K] = bf16(dZ [M][N]) . bf16(W [N][K])
+ *   grx_mlp_weight_grad_bf16: dW [N][K] = bf16(dZ [M][N])^T . bf16(X [M][K]), summed over the M batch rows in slabs of rows;
+ *                             `partials`: scratch of grx_mlp_weight_grad_bf16_partials_size(M, N, K) floats (0: invalid sizes) */
+int grx_mlp_layer_bf16(int M, int K, int N, const float* X, const float* W, const float* bias, float* Y, int elu, void* stream);
+int grx_mlp_input_grad_bf16(int M, int N, int K, const float* dZ, const float* W, float* dX, void* stream);
+int grx_mlp_weight_grad_bf16_partials_size(int M, int N, int K);
+int grx_mlp_weight_grad_bf16(int M, int N, int K, const float* dZ, const float* X, float* dW, float* partials, void* stream);
+
 /* The actor's output layer fused with the rollout's sampling and log-probability (actor_critic_mlp.py act() /
  * get_actions_log_prob() -> torch.distributions.Normal): mu = X . W^T + bias, actions = mu + std * eps,
  * logp = sum_k -(a - mu)^2 / (2 std^2) - log(std) - log(sqrt(2 pi)); sigma = std broadcast to (M, A).

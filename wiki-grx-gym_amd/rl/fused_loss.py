@@ -39,6 +39,14 @@ def load_ppo_library():
         lib.grx_ppo_gather_rows.argtypes = [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int), fp, C.c_int, C.c_void_p]
         lib.grx_mlp_layer.restype = C.c_int
         lib.grx_mlp_layer.argtypes = [C.c_int] * 3 + [fp] * 4 + [C.c_int, C.c_void_p]
+        lib.grx_mlp_layer_bf16.restype = C.c_int
+        lib.grx_mlp_layer_bf16.argtypes = [C.c_int] * 3 + [fp] * 4 + [C.c_int, C.c_void_p]
+        lib.grx_mlp_input_grad_bf16.restype = C.c_int
+        lib.grx_mlp_input_grad_bf16.argtypes = [C.c_int] * 3 + [fp] * 3 + [C.c_void_p]
+        lib.grx_mlp_weight_grad_bf16_partials_size.restype = C.c_int
+        lib.grx_mlp_weight_grad_bf16_partials_size.argtypes = [C.c_int] * 3
+        lib.grx_mlp_weight_grad_bf16.restype = C.c_int
+        lib.grx_mlp_weight_grad_bf16.argtypes = [C.c_int] * 3 + [fp] * 4 + [C.c_void_p]
         lib.grx_mlp_policy_head.restype = C.c_int
         lib.grx_mlp_policy_head.argtypes = [C.c_int] * 3 + [fp] * 9 + [C.c_void_p]
         lib.grx_ppo_step_tail.restype = C.c_int
@@ -251,31 +259,68 @@ def mlp_can_fuse(mlp, x):
     return x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and _linears_of(mlp) is not None
 
 
-def _layer(lib, x, w, b, elu, stream):
+def _layer(lib, x, w, b, elu, stream, bf16=False):
     y = torch.empty(x.shape[0], w.shape[0], device=x.device, dtype=torch.float32)
-    rc = lib.grx_mlp_layer(x.shape[0], x.shape[1], w.shape[0], x.data_ptr(), w.data_ptr(), b.data_ptr() if b is not None else None,
-                           y.data_ptr(), int(elu), stream)
+    fn = lib.grx_mlp_layer_bf16 if bf16 else lib.grx_mlp_layer
+    rc = fn(x.shape[0], x.shape[1], w.shape[0], x.data_ptr(), w.data_ptr(), b.data_ptr() if b is not None else None, y.data_ptr(), int(elu), stream)
     if rc:
-        raise RuntimeError(f"grx_mlp_layer failed ({rc})")
+        raise RuntimeError(f"{'grx_mlp_layer_bf16' if bf16 else 'grx_mlp_layer'} failed ({rc}): {tuple(x.shape)} x {tuple(w.shape)}")
     return y
 
 
-def linear_elu(x, weight, bias):
-    """ELU(x W^T + b) through grx_mlp_layer (one launch)"""
+def _bf16_hidden(mlp):
+    """True when an rl.modules.MLP multiplies its hidden layers in bf16 (MLP.set_precision)"""
+    return getattr(mlp, "precision", "fp32") == "bf16"
+
+
+def linear_elu(x, weight, bias, bf16=False):
+    """ELU(x W^T + b) through grx_mlp_layer, or grx_mlp_layer_bf16 with bf16 operands (one launch)"""
     lib = load_ppo_library()
     with torch.cuda.device(x.device):
-        return _layer(lib, x, weight, bias, True, torch.cuda.current_stream(x.device).cuda_stream)
+        return _layer(lib, _f32c(x), _f32c(weight), bias, True, torch.cuda.current_stream(x.device).cuda_stream, bf16)
+
+
+def input_grad_bf16(dz, weight):
+    """dX = bf16(dZ) . bf16(W) through grx_mlp_input_grad_bf16: dz [M, N], weight [N, K] -> [M, K] (fp32)"""
+    lib = load_ppo_library()
+    dz, weight = _f32c(dz), _f32c(weight)
+    (M, N), K = dz.shape, weight.shape[1]
+    dx = torch.empty(M, K, device=dz.device, dtype=torch.float32)
+    with torch.cuda.device(dz.device):
+        rc = lib.grx_mlp_input_grad_bf16(M, N, K, dz.data_ptr(), weight.data_ptr(), dx.data_ptr(),
+                                         C.c_void_p(torch.cuda.current_stream(dz.device).cuda_stream))
+    if rc:
+        raise RuntimeError(f"grx_mlp_input_grad_bf16 failed ({rc}): {M} x {N} x {K}")
+    return dx
+
+
+def weight_grad_bf16(dz, x):
+    """dW = bf16(dZ)^T . bf16(X) through grx_mlp_weight_grad_bf16 (batch slabs added in a fixed order): dz [M, N], x [M, K] -> [N, K]"""
+    lib = load_ppo_library()
+    dz, x = _f32c(dz), _f32c(x)
+    (M, N), K = dz.shape, x.shape[1]
+    dw = torch.empty(N, K, device=dz.device, dtype=torch.float32)
+    partials = torch.empty(max(1, lib.grx_mlp_weight_grad_bf16_partials_size(M, N, K)), device=dz.device, dtype=torch.float32)
+    with torch.cuda.device(dz.device):
+        rc = lib.grx_mlp_weight_grad_bf16(M, N, K, dz.data_ptr(), x.data_ptr(), dw.data_ptr(), partials.data_ptr(),
+                                          C.c_void_p(torch.cuda.current_stream(dz.device).cuda_stream))
+    if rc:
+        raise RuntimeError(f"grx_mlp_weight_grad_bf16 failed ({rc}): {M} x {N} x {K}")
+    return dw
 
 
 def mlp_forward(mlp, x):
-    """Inference forward of an rl.modules.MLP through libgrx_ppo.so: one MFMA launch per layer (bias + ELU in the epilogue)."""
+    """Inference forward of an rl.modules.MLP through libgrx_ppo.so: one MFMA launch per layer (bias + ELU in the epilogue); the
+    hidden layers with bf16 operands when the MLP is set to bf16 (the output layer stays fp32)."""
     lib = load_ppo_library()
     lin = _linears_of(mlp)
+    bf16 = _bf16_hidden(mlp)
     x = _f32c(x)
     stream = torch.cuda.current_stream(x.device).cuda_stream
     with torch.cuda.device(x.device):
         for i, (w, b) in enumerate(lin):
-            x = _layer(lib, x, w, b, i + 1 < len(lin), stream)
+            hidden = i + 1 < len(lin)
+            x = _layer(lib, x, w, b, hidden, stream, bf16 and hidden)
     return x
 
 
@@ -284,11 +329,12 @@ def policy_act(mlp, std, x, eps):
     layer fused with `mu + std * eps` and Normal.log_prob summed over the actions."""
     lib = load_ppo_library()
     lin = _linears_of(mlp)
+    bf16 = _bf16_hidden(mlp)
     x = _f32c(x)
     stream = torch.cuda.current_stream(x.device).cuda_stream
     with torch.cuda.device(x.device):
         for w, b in lin[:-1]:
-            x = _layer(lib, x, w, b, True, stream)
+            x = _layer(lib, x, w, b, True, stream, bf16)
         w, b = lin[-1]
         M, A = x.shape[0], w.shape[0]
         actions, mu, sigma = (torch.empty(M, A, device=x.device, dtype=torch.float32) for _ in range(3))

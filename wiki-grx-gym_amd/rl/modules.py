@@ -11,6 +11,7 @@ import torch
 import torch.nn as nn
 from torch.distributions import Normal
 
+PRECISIONS = ("fp32", "bf16")   # PPO(precision=...): the hidden layers' matrix products
 _ACTIVATIONS = {"elu": nn.ELU, "selu": nn.SELU, "relu": nn.ReLU, "crelu": nn.ReLU, "lrelu": nn.LeakyReLU,
                 "tanh": nn.Tanh, "sigmoid": nn.Sigmoid}
 
@@ -75,11 +76,19 @@ class _TrainLinear(torch.autograd.Function):
 class _TrainLinearELU(torch.autograd.Function):
     """ELU(x W^T + b) of a hidden layer as PPO trains it on a HIP device: _TrainLinear's products, with the ELU's backward and the
     bias gradient in ONE pass over dY (fused_loss.elu_backward_colsum: dZ = dY * ELU'(Y) from the saved OUTPUT, column sums of dZ)
-    instead of an elu_backward launch followed by the column sum."""
+    instead of an elu_backward launch followed by the column sum.
+
+    bf16=True (MLP.set_precision("bf16")): the three products -- Y, dX, dW -- run on libgrx_ppo.so's bf16 kernels, which round
+    both operands to bf16 as they load them and accumulate in fp32.  The bias gradient, the ELU backward and every tensor in
+    memory stay fp32."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias):
-        if _FUSED_ELU_FORWARD and x.is_contiguous() and weight.is_contiguous():
+    def forward(ctx, x, weight, bias, bf16):
+        ctx.bf16 = bf16
+        if bf16:
+            from .fused_loss import linear_elu
+            y = linear_elu(x, weight, bias, bf16=True)
+        elif _FUSED_ELU_FORWARD and x.is_contiguous() and weight.is_contiguous():
             from .fused_loss import linear_elu
             y = linear_elu(x, weight, bias)   # libgrx_ppo.so: f32 MFMA, bias + ELU in the epilogue (one launch)
         else:
@@ -96,10 +105,14 @@ class _TrainLinearELU(torch.autograd.Function):
         from .fused_loss import elu_backward_colsum
         x, weight, y = ctx.saved_tensors
         dz, db = elu_backward_colsum(dy, y)
+        if ctx.bf16:
+            from .fused_loss import input_grad_bf16, weight_grad_bf16
+            dx = input_grad_bf16(dz, weight) if ctx.needs_input_grad[0] else None   # (the first layer's input is data: no dX product)
+            return dx, weight_grad_bf16(dz, x), db, None
         prev = _TrainLinear._blas(weight.shape[0] == 1)
         try:
             dx = dz @ weight if ctx.needs_input_grad[0] else None   # (the first layer's input is data: no dX product)
-            return dx, dz.t() @ x, db
+            return dx, dz.t() @ x, db, None
         finally:
             torch.backends.cuda.preferred_blas_library(prev)
 
@@ -114,16 +127,37 @@ class MLP(nn.Module):
             layers += [nn.Linear(a, b), get_activation(activation)]
         layers.append(nn.Linear(dims[-1], output_size))
         self.model = nn.Sequential(*layers)
+        self.precision = "fp32"
+
+    def set_precision(self, precision):
+        """"fp32" (default) or "bf16": the hidden layers' products with bf16 operands and fp32 accumulation (libgrx_ppo.so, HIP
+        devices only; the output layer, the parameters and every activation stay fp32).  bf16 needs Linear -> ELU(1) hidden layers."""
+        if precision not in PRECISIONS:
+            raise ValueError(f"precision must be one of {PRECISIONS}, not {precision!r}")
+        if precision == "bf16":
+            from .fused_loss import _linears_of
+            if _linears_of(self) is None:
+                raise ValueError("precision='bf16' needs an MLP of Linear -> ELU(alpha=1) hidden layers")
+        self.precision = precision
 
     @torch.jit.unused
-    def _forward_train(self, x):
+    def _forward_bf16(self, x):
+        if not (x.is_cuda and x.dtype == torch.float32):
+            raise RuntimeError("an MLP set to precision='bf16' runs on a HIP device with fp32 input only (there is no CPU path)")
+        if torch.is_grad_enabled():
+            return self._forward_train(x, bf16=True)
+        from .fused_loss import mlp_forward   # (inference: the kernels the rollout's captured policy step runs)
+        return mlp_forward(self, x.reshape(-1, x.shape[-1])).reshape(*x.shape[:-1], self.output_size)
+
+    @torch.jit.unused
+    def _forward_train(self, x, bf16=False):
         mods = list(self.model)
         i = 0
         while i < len(mods):
             m = mods[i]
             if isinstance(m, nn.Linear) and i + 1 < len(mods) and isinstance(mods[i + 1], nn.ELU) and mods[i + 1].alpha == 1.0 \
-                    and _FUSED_ELU_BACKWARD:
-                x = _TrainLinearELU.apply(x, m.weight, m.bias)
+                    and (_FUSED_ELU_BACKWARD or bf16):
+                x = _TrainLinearELU.apply(x, m.weight, m.bias, bf16)
                 i += 2
                 continue
             x = _TrainLinear.apply(x, m.weight, m.bias) if isinstance(m, nn.Linear) else m(x)
@@ -132,6 +166,8 @@ class MLP(nn.Module):
 
     def forward(self, x):
         if not torch.jit.is_scripting():   # (export_policy_as_jit scripts this module: the plain path)
+            if self.precision == "bf16":
+                return self._forward_bf16(x)
             if x.is_cuda and torch.is_grad_enabled() and x.dtype == torch.float32 and _TRAIN_LINEAR == "colsum":
                 return self._forward_train(x)   # training on a HIP device: see _TrainLinear
         return self.model(x)
@@ -175,6 +211,11 @@ class ActorCriticMLP(nn.Module):
             self.std.requires_grad = False
             state_dict["std"] = self.std.detach().clone()
         return super().load_state_dict(state_dict, strict)
+
+    def set_precision(self, precision):
+        """the hidden layers of actor and critic in "fp32" or "bf16" (MLP.set_precision; PPO(precision=...) calls this)"""
+        self.actor.set_precision(precision)
+        self.critic.set_precision(precision)
 
     def reset(self, dones=None):
         pass

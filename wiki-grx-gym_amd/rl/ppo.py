@@ -16,7 +16,7 @@ from .fused_loss import fused_ppo_loss, mlp_can_fuse, mlp_forward, policy_act
 import torch.nn as nn
 import torch.optim as optim
 
-from .modules import ActorCriticMLP  # noqa: F401
+from .modules import PRECISIONS, ActorCriticMLP  # noqa: F401
 from .storage import RolloutStorage
 
 
@@ -62,13 +62,25 @@ class PPO:
     def __init__(self, actor_critic=None, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998, lam=0.95,
                  value_loss_coef=1.0, entropy_coef=0.0, learning_rate=1e-3, learning_rate_min=1e-5, learning_rate_max=1e-2,
                  weight_decay=0.0, max_grad_norm=1.0, use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01,
-                 device="cpu", storage_class="RolloutStorage", **kwargs):
+                 device="cpu", storage_class="RolloutStorage", precision="fp32", **kwargs):
         if kwargs:
             print("PPO.__init__ got unexpected arguments, which will be ignored: " + str(list(kwargs)))
+        # precision="bf16": every hidden layer of actor and critic multiplies bf16 operands into fp32 accumulators -- in the rollout's
+        # policy step and in every product of the update (rl/modules.py MLP.set_precision).  Output heads, parameters, gradients, Adam
+        # state and activations stay fp32.  Not a config key: `--precision` or an assignment to train_cfg.algorithm sets it.
+        if precision not in PRECISIONS:
+            raise ValueError(f"PPO: precision must be one of {PRECISIONS}, not {precision!r}")
+        if precision == "bf16" and torch.device(device).type != "cuda":
+            raise ValueError(f"PPO: precision='bf16' runs on a HIP device only, not on {device!r} (there is no CPU path)")
+        if precision != "fp32" and not hasattr(actor_critic, "set_precision"):
+            raise ValueError(f"PPO: {type(actor_critic).__name__} has no set_precision(): precision={precision!r} is not available")
+        self.precision = precision
         self.device = device
         self.desired_kl, self.schedule, self.mean_kl = desired_kl, schedule, 0.0
         self.learning_rate, self.learning_rate_min, self.learning_rate_max = learning_rate, learning_rate_min, learning_rate_max
         self.actor_critic = actor_critic.to(device)
+        if hasattr(self.actor_critic, "set_precision"):
+            self.actor_critic.set_precision(precision)
         self.storage_class = storage_class
         self.storage, self.transition = None, None
         # On a HIP device the whole update runs without host synchronisation: the adaptive learning rate lives in a

@@ -56,6 +56,8 @@ def get_args(argv=None):
     p.add_argument("--subscenes", type=int, default=0, help="accepted for compatibility")
     p.add_argument("--slices", type=int)
     p.add_argument("--terrain", type=str, choices=["plane", "heightfield", "trimesh"], help="override cfg.terrain.mesh_type")
+    p.add_argument("--precision", type=str, choices=["fp32", "bf16"],
+                   help="PPO's hidden-layer matrix products: fp32 (default) or bf16 operands with fp32 accumulation (HIP only)")
     args = p.parse_args(argv)
     args.sim_device_type, args.compute_device_id = parse_device_str(args.sim_device)
     args.use_gpu_pipeline = args.pipeline.lower() in ("gpu", "cuda")
@@ -86,6 +88,8 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
         for name in ("experiment_name", "run_name", "load_run", "checkpoint"):
             if getattr(args, name) is not None:
                 setattr(cfg_train.runner, name, getattr(args, name))
+        if getattr(args, "precision", None) is not None:   # (only when given: the algorithm config has no such key otherwise)
+            cfg_train.algorithm.precision = args.precision
     return env_cfg, cfg_train
 
 
