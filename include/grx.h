@@ -502,6 +502,23 @@ int grx_layout(grx_handle h, grx_layout_info* out);
  * kernel stores, when it STARTS, the ticket of the step before it -- complete by stream order), see grx_capi.cpp. */
 int grx_wait_idle(grx_handle h);
 
+/* Snapshot / restore of a handle's mutable state: an exact training resume across processes.
+ * The blob holds every device buffer a later launch reads or a grx_tensor view exposes (the SoA state, timers, episode sums, terrain
+ * levels / types / origins, the output tensors, the pre-reset stash, the statistics partials and history ring, the command ranges of a
+ * curriculum handle) and the host counters that shape the next launch.  It does NOT hold what grx_create derives from its inputs (the
+ * domain-randomisation values, the terrain raster and the robot tables): its header carries a fingerprint of those inputs and of the
+ * launched layout instead.
+ *   grx_state_bytes: size of this handle's blob.
+ *   grx_save_state:  copy the blob to host memory (bytes must equal grx_state_bytes); synchronises `stream`, where the handle's work
+ *                    was enqueued.  Not while `stream` records a graph.
+ *   grx_load_state:  restore a blob into a handle created from the same inputs.  The header (size, ABI, fingerprint, checksum) is checked
+ *                    before anything is written: on a mismatch GRX_ERR_INVALID_ARGUMENT, grx_last_error() says why, the handle is unchanged.
+ *                    Synchronises `stream`; GRX_T_RIGID_BODY_STATES / GRX_T_MEASURED_HEIGHTS published on refresh are materialised anew on
+ *                    the next grx_refresh. */
+int grx_state_bytes(grx_handle h, int64_t* bytes);
+int grx_save_state(grx_handle h, void* host_dst, int64_t bytes, void* stream);
+int grx_load_state(grx_handle h, const void* host_src, int64_t bytes, void* stream);
+
 /* ---- TEST-ONLY entry (not part of the drop-in surface; the reference has no counterpart) ----------------------
  * State injected into the post-physics half of the step: the same record the CPU oracle's gro_debug_post_physics
  * takes, so that tests/ can present the reference's golden fixtures (tools/gen_golden.py: legged_robot.py:269-481,

@@ -240,6 +240,10 @@ def bind(lib, prefix="grx_"):
         api["sizeof"] = fn("sizeof", C.c_int, C.c_int)
     if hasattr(lib, prefix + "kernel_time_ms"):
         api["kernel_time_ms"] = fn("kernel_time_ms", C.c_int, H, C.c_int, C.POINTER(C.c_float), C.POINTER(i64))
+    if hasattr(lib, prefix + "save_state") and prefix == "grx_":   # snapshot / restore of a handle (exact training resume)
+        api["state_bytes"] = fn("state_bytes", C.c_int, H, C.POINTER(i64))
+        api["save_state"] = fn("save_state", C.c_int, H, C.c_void_p, i64, C.c_void_p)
+        api["load_state"] = fn("load_state", C.c_int, H, C.c_void_p, i64, C.c_void_p)
     return api
 
 
@@ -247,7 +251,7 @@ EXPORTED_SYMBOLS = (
     "grx_create", "grx_destroy", "grx_reset_all", "grx_step", "grx_tensor", "grx_set_state",
     "grx_episode_stats", "grx_flush_stats", "grx_reset_idx", "grx_set_state_indexed", "grx_kernel_time_ms", "grx_wait_idle", "grx_last_error", "grx_abi_version",
     "grx_reward_term_name", "grx_debug_post_physics", "grx_layout", "grx_stats_seq", "grx_debug_spin_report", "grx_sizeof", "grx_refresh", "grx_debug_terrain", "grx_debug_wall", "grx_debug_trimesh_tables",
-    "grx_base_reward_term_name",
+    "grx_base_reward_term_name", "grx_state_bytes", "grx_save_state", "grx_load_state",
 )
 # grx_struct_id (include/grx.h): grx_sizeof(id) must equal ctypes.sizeof of the mirror -- checked once per process by sim.load_hip_library
 STRUCT_IDS = {"CONFIG": (0, Config), "STEP_ARGS": (1, StepArgs), "TENSOR_DESC": (2, TensorDesc), "PIPELINE_STATE": (3, PipelineState),

@@ -156,6 +156,8 @@ struct grx_sim {
     bool spin_bounded = false;    // a -DGRX_SPIN_LIMIT build: LDS spins are bounded and report through pace.progress[1]
     float* d_dbg = nullptr;       // grx_debug_post_physics: injected quantities [grx_debug_rows()][N]
     float* d_dbg_actions = nullptr;   // ... and the injected (already clipped) actions, (N, nd) row-major
+    size_t ws_floats = 0;         // floats of the generic workspace d_ws
+    uint64_t fingerprint = 0;     // grx_save_state / grx_load_state: hash of the creation inputs and the launched layout (state_fingerprint)
 };
 
 namespace {
@@ -698,7 +700,8 @@ int build_generic(grx_sim* s, const grx_config& c) {
     if (rc) return rc;
     HIP_TRY(hipMemcpy(d, &T, sizeof T, hipMemcpyHostToDevice));
     s->d_gen = d;
-    rc = dalloc(s, &s->d_ws, (size_t)grx_generic_ws_floats_per_env(T.nb, T.nlc) * (size_t)s->N);
+    s->ws_floats = (size_t)grx_generic_ws_floats_per_env(T.nb, T.nlc) * (size_t)s->N;
+    rc = dalloc(s, &s->d_ws, s->ws_floats);
     if (rc) return rc;
     // ---- the lane-group tree kernel (grx_tree.h): chains of the tree -> lanes, depth levels -> steps
     if (const char* tv_ = getenv("GRX_TREE")) if (atoi(tv_) == 0) return GRX_OK;
@@ -839,6 +842,104 @@ int build_generic(grx_sim* s, const grx_config& c) {
     s->d_tree = dk; s->tree_lds = lds;
     return GRX_OK;
 }
+}  // namespace
+
+// ---- grx_save_state / grx_load_state (include/grx.h): what a snapshot holds and how it is checked
+namespace {
+constexpr uint64_t kStateMagic = 0x3154415453585247ull;   // "GRXSTAT1"
+constexpr int32_t kStateFormat = 1;
+
+uint64_t fnv1a(uint64_t h, const void* p, size_t n) {
+    const unsigned char* b = static_cast<const unsigned char*>(p);
+    for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 0x100000001b3ull; }
+    return h;
+}
+template <typename T> uint64_t fnv_val(uint64_t h, const T& v) { return fnv1a(h, &v, sizeof v); }
+
+// the creation inputs a snapshot is only valid for: grx_config (its two host pointers cleared) with the model, N, env_offset and seed in it;
+// the raster and the terrain origins behind those pointers; the layout grx_create picked (grx_layout, environment overrides included) and
+// the launch parameters environment variables can change
+uint64_t state_fingerprint(grx_sim* s, const grx_config& c) {
+    uint64_t h = 0xcbf29ce484222325ull;
+    h = fnv1a(h, &s->cfg, sizeof s->cfg);   // (height_samples / terrain_origins are nullptr in the handle's copy)
+    if (c.terrain_type == GRX_TERRAIN_HEIGHTFIELD) {
+        h = fnv1a(h, c.height_samples, (size_t)c.hf_rows * c.hf_cols * sizeof(int16_t));
+        h = fnv1a(h, c.terrain_origins, (size_t)c.num_terrain_rows * c.num_terrain_cols * 3 * sizeof(float));
+    }
+    grx_layout_info li;
+    if (grx_layout(s, &li) == GRX_OK) h = fnv1a(h, &li, sizeof li);
+    const KParams& P = s->hp;
+    for (int32_t v : {s->N, s->nd, (int)s->generic, (int)s->quad, (int)s->base, s->base_cols, s->waves, s->tree_g, s->tree_waves, s->gen_epb, s->gen_lds,
+                      (int)(s->d_tree != nullptr), s->rbs_mode, s->heights_mode, P.self_collisions, P.publish_debug, P.publish_rbs, P.publish_heights,
+                      P.stash_pre_reset, P.stat_stride, (int32_t)P.base_active})
+        h = fnv_val(h, v);
+    h = fnv_val(h, P.bounce_threshold);
+    return h;
+}
+
+struct StateRegion { void* p; size_t bytes; };
+
+// every device buffer of the handle that is state: written by a launch and read by a later one, or exposed through grx_tensor
+std::vector<StateRegion> state_regions(const grx_sim* s) {
+    const KParams& P = s->hp;
+    const size_t N = (size_t)s->N, nd = (size_t)s->nd, nh = (size_t)(P.nh > 0 ? P.nh : 1);
+    constexpr size_t NB = GRX_NUM_BASE_REWARD_TERMS;
+    std::vector<StateRegion> r;
+    auto add = [&](const void* p, size_t bytes) { if (p && bytes) r.push_back({const_cast<void*>(p), bytes}); };
+#define GRX_REGION(field, count) add(P.field, (size_t)(count) * sizeof(*P.field))
+    GRX_REGION(q, nd * N); GRX_REGION(qd, nd * N); GRX_REGION(root, 13 * N); GRX_REGION(anchors, 24 * N);
+    GRX_REGION(last_actions, nd * N); GRX_REGION(last_dof_vel, nd * N); GRX_REGION(actions, nd * N); GRX_REGION(torques, nd * N);
+    GRX_REGION(commands, 3 * N); GRX_REGION(origins, 3 * N); GRX_REGION(levels, N); GRX_REGION(types, N);
+    GRX_REGION(air_time, 2 * N); GRX_REGION(land_time, 2 * N); GRX_REGION(feet_contact, 2 * N);
+    GRX_REGION(feet_height, 2 * N); GRX_REGION(avg_force, 2 * N); GRX_REGION(feet_force, 6 * N); GRX_REGION(contact_forces, 3 * GRX_MAX_LINKS * N);
+    GRX_REGION(feet_pos, 6 * N); GRX_REGION(avg_speed, 6 * N); GRX_REGION(avg_speed_rpy, 6 * N);
+    GRX_REGION(base_heights_offset, N); GRX_REGION(ep_len, N); GRX_REGION(rew, N); GRX_REGION(reset, N); GRX_REGION(time_out, N); GRX_REGION(term_contact, N);
+    GRX_REGION(base_lin_vel, 3 * N); GRX_REGION(base_ang_vel, 3 * N); GRX_REGION(proj_grav, 3 * N);
+    GRX_REGION(episode_sums, NT * N); GRX_REGION(reward_terms, NT * N); GRX_REGION(heights, nh * N);
+    GRX_REGION(obs, (size_t)s->cfg.num_obs * N + 64); GRX_REGION(pri_obs, (size_t)s->cfg.num_pri_obs * N + 64);
+    GRX_REGION(stat_partial, 2 * NSTAT * (size_t)P.stat_stride); GRX_REGION(stat_nblocks, 2);
+    GRX_REGION(stat_hist, (size_t)GRX_STATS_HISTORY * NSTAT); GRX_REGION(stats, NSTAT);
+    if (s->base) {
+        GRX_REGION(base_episode_sums, NB * N); GRX_REGION(base_reward_terms, NB * N);
+        GRX_REGION(base_stat_partial, (NB + 1) * (size_t)P.stat_stride); GRX_REGION(base_stats, NB); GRX_REGION(base_stat_hist, (size_t)GRX_STATS_HISTORY * NB);
+    }
+    if (s->rbs_mode != GRX_PUBLISH_NEVER) GRX_REGION(rbs, 13 * GRX_MAX_LINKS * N);
+    if (P.stash_pre_reset) { GRX_REGION(pre_q, nd * N); GRX_REGION(pre_qd, nd * N); GRX_REGION(pre_root, 13 * N); GRX_REGION(pre_push_vel, 2 * N); }
+#undef GRX_REGION
+    add(s->d_mask, N);
+    add(s->d_ws, s->ws_floats * sizeof(float));
+    // the command ranges the kernels draw from live in the device copy of KParams (the curriculum kernel widens them there)
+    add(reinterpret_cast<char*>(s->d_hp) + offsetof(KParams, cmd_lin_vel_x), 6 * sizeof(float));
+    return r;
+}
+
+// the host counters that shape the next launch (statistics parity and folding, the reset draws' step number, the refresh of a push step)
+struct StateCounters {
+    int64_t seq, eager_seq;
+    uint32_t reset_count;
+    uint8_t stats_current, last_pushed, prev_recorded, pad;
+};
+
+struct StateHeader {
+    uint64_t magic;
+    int32_t abi_version, format;
+    int64_t bytes;          // the whole blob, header included
+    uint64_t fingerprint;   // state_fingerprint of the handle that wrote it
+    uint64_t checksum;      // FNV-1a of everything behind the header
+    StateCounters counters;
+};
+
+size_t state_payload_bytes(const std::vector<StateRegion>& r) {
+    size_t n = 0;
+    for (const StateRegion& x : r) n += x.bytes;
+    return n;
+}
+
+// pinned staging for one copy in either direction, freed on every path
+struct PinnedBuffer {
+    void* p = nullptr;
+    ~PinnedBuffer() { if (p) hipHostFree(p); }
+};
 }  // namespace
 
 extern "C" {
@@ -1353,6 +1454,7 @@ int grx_create(const grx_config* cfg, int device_id, grx_handle* out) {
                           offsetof(KParams, cmd_ang_vel_yaw) == offsetof(KParams, cmd_lin_vel_x) + 4 * sizeof(float), "the three ranges must be one (3, 2) block");
         }
     }
+    s->fingerprint = state_fingerprint(s, c);
     *out = s;
     return GRX_OK;
 }
@@ -1806,6 +1908,72 @@ int grx_wait_idle(grx_handle s) {
         HIP_TRY(hipGetLastError());
     }
     return spin_until(s, s->pace.issued, "grx_wait_idle");
+}
+
+int grx_state_bytes(grx_handle s, int64_t* bytes) {
+    if (!s || !bytes) return fail(GRX_ERR_INVALID_ARGUMENT, "grx_state_bytes: null argument");
+    *bytes = (int64_t)(sizeof(StateHeader) + state_payload_bytes(state_regions(s)));
+    return GRX_OK;
+}
+
+int grx_save_state(grx_handle s, void* host_dst, int64_t bytes, void* stream) {
+    if (!s || !host_dst) return fail(GRX_ERR_INVALID_ARGUMENT, "grx_save_state: null argument");
+    const std::vector<StateRegion> regions = state_regions(s);
+    const size_t payload = state_payload_bytes(regions);
+    if (bytes != (int64_t)(sizeof(StateHeader) + payload))
+        return fail(GRX_ERR_INVALID_ARGUMENT, "grx_save_state: bytes must equal grx_state_bytes() (" + std::to_string(sizeof(StateHeader) + payload) + ")");
+    hipStream_t st = (hipStream_t)stream;
+    if (stream_is_capturing(st)) return fail(GRX_ERR_INVALID_ARGUMENT, "grx_save_state: the stream is recording a graph");
+    PinnedBuffer stage;
+    HIP_TRY(hipHostMalloc(&stage.p, payload, hipHostMallocDefault));
+    size_t off = 0;
+    for (const StateRegion& x : regions) {
+        HIP_TRY(hipMemcpyAsync(static_cast<char*>(stage.p) + off, x.p, x.bytes, hipMemcpyDeviceToHost, st));
+        off += x.bytes;
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    StateHeader hd;
+    memset(&hd, 0, sizeof hd);
+    hd.magic = kStateMagic; hd.abi_version = GRX_ABI_VERSION; hd.format = kStateFormat; hd.bytes = bytes; hd.fingerprint = s->fingerprint;
+    hd.checksum = fnv1a(0xcbf29ce484222325ull, stage.p, payload);
+    hd.counters.seq = s->seq; hd.counters.eager_seq = s->eager_seq; hd.counters.reset_count = s->reset_count;
+    hd.counters.stats_current = s->stats_current ? 1 : 0; hd.counters.last_pushed = s->last_pushed ? 1 : 0; hd.counters.prev_recorded = s->prev_recorded ? 1 : 0;
+    memcpy(host_dst, &hd, sizeof hd);
+    memcpy(static_cast<char*>(host_dst) + sizeof hd, stage.p, payload);
+    return GRX_OK;
+}
+
+int grx_load_state(grx_handle s, const void* host_src, int64_t bytes, void* stream) {
+    if (!s || !host_src) return fail(GRX_ERR_INVALID_ARGUMENT, "grx_load_state: null argument");
+    const std::vector<StateRegion> regions = state_regions(s);
+    const size_t payload = state_payload_bytes(regions);
+    if (bytes < (int64_t)sizeof(StateHeader)) return fail(GRX_ERR_INVALID_ARGUMENT, "grx_load_state: blob shorter than its header");
+    StateHeader hd;
+    memcpy(&hd, host_src, sizeof hd);
+    if (hd.magic != kStateMagic || hd.format != kStateFormat) return fail(GRX_ERR_INVALID_ARGUMENT, "grx_load_state: not a grx_save_state blob");
+    if (hd.abi_version != GRX_ABI_VERSION) return fail(GRX_ERR_INVALID_ARGUMENT, "grx_load_state: blob written by ABI " + std::to_string(hd.abi_version));
+    if (hd.bytes != bytes || bytes != (int64_t)(sizeof(StateHeader) + payload))
+        return fail(GRX_ERR_INVALID_ARGUMENT, "grx_load_state: blob of " + std::to_string(bytes) + " B, this handle's state has " + std::to_string(sizeof(StateHeader) + payload) + " B");
+    if (hd.fingerprint != s->fingerprint)
+        return fail(GRX_ERR_INVALID_ARGUMENT, "grx_load_state: the blob was written by a handle created from other inputs (config, model, envs, seed, terrain or layout)");
+    const char* body = static_cast<const char*>(host_src) + sizeof hd;
+    if (hd.checksum != fnv1a(0xcbf29ce484222325ull, body, payload)) return fail(GRX_ERR_INVALID_ARGUMENT, "grx_load_state: checksum mismatch (corrupted blob)");
+    hipStream_t st = (hipStream_t)stream;
+    if (stream_is_capturing(st)) return fail(GRX_ERR_INVALID_ARGUMENT, "grx_load_state: the stream is recording a graph");
+    PinnedBuffer stage;
+    HIP_TRY(hipHostMalloc(&stage.p, payload, hipHostMallocDefault));
+    memcpy(stage.p, body, payload);
+    size_t off = 0;
+    for (const StateRegion& x : regions) {
+        HIP_TRY(hipMemcpyAsync(x.p, static_cast<const char*>(stage.p) + off, x.bytes, hipMemcpyHostToDevice, st));
+        off += x.bytes;
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    s->seq = hd.counters.seq; s->eager_seq = hd.counters.eager_seq; s->reset_count = hd.counters.reset_count;
+    s->stats_current = hd.counters.stats_current != 0; s->last_pushed = hd.counters.last_pushed != 0; s->prev_recorded = hd.counters.prev_recorded != 0;
+    s->rbs_seq = s->heights_seq = -1;   // the on-demand tensors are materialised anew
+    ++s->state_epoch;
+    return GRX_OK;
 }
 
 const char* grx_last_error(void) { return g_err.c_str(); }

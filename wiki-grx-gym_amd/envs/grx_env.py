@@ -343,6 +343,45 @@ class GRxEnv:
         """gym.set_actor_root_state_tensor_indexed (legged_robot.py:782-784): rows env_ids of a full (N, 13) tensor"""
         self._sim.set_state_indexed(env_ids, root_states.contiguous(), None, None)
 
+    # ------------------------------------------------------------------ exact resume (DESIGN.md 4.6)
+    def get_state(self):
+        """Everything a later step() depends on, as host data: the library's snapshot of the handle (include/grx.h grx_save_state),
+        the step counter, both observation buffers and which of them obs_buf / pri_obs_buf are, numpy's global generator (the
+        action-delay draw) and fixed_action_delay.  set_state() on an env built from the same config continues bit for bit."""
+        return {
+            "sim": self._sim.save_state(),
+            "common_step_counter": int(self.common_step_counter),
+            "obs_ring": [b.cpu() for b in self._obs_ring],
+            "pri_ring": [b.cpu() for b in self._pri_ring] if self._pri_ring is not None else None,
+            "ring": int(self._ring),
+            "obs_buf": next(i for i, b in enumerate(self._obs_ring) if b is self.obs_buf),
+            "pri_obs_buf": next(i for i, b in enumerate(self._pri_ring) if b is self.pri_obs_buf) if self._pri_ring is not None else None,
+            "np_random": np.random.get_state(),
+            "fixed_action_delay": self.fixed_action_delay,
+        }
+
+    def set_state(self, state):
+        """Restore get_state() of an env built from the same config; raises, with this env unchanged, on any mismatch."""
+        def same_ring(saved, ring):
+            if (saved is None) != (ring is None):
+                return False
+            return saved is None or (len(saved) == len(ring) and all(tuple(a.shape) == tuple(b.shape) and a.dtype == b.dtype for a, b in zip(saved, ring)))
+        if not same_ring(state["obs_ring"], self._obs_ring) or not same_ring(state["pri_ring"], self._pri_ring):
+            raise ValueError("GRxEnv.set_state: the observation buffers differ in shape (another num_envs / num_obs / num_pri_obs)")
+        self._sim.load_state(state["sim"])   # (checks the handle's creation inputs before it writes anything)
+        for dst, src in zip(self._obs_ring, state["obs_ring"]):
+            dst.copy_(src)
+        if self._pri_ring is not None:
+            for dst, src in zip(self._pri_ring, state["pri_ring"]):
+                dst.copy_(src)
+        self._ring = int(state["ring"])
+        self.obs_buf = self._obs_ring[state["obs_buf"]]
+        self.pri_obs_buf = self._pri_ring[state["pri_obs_buf"]] if self._pri_ring is not None else None
+        self.common_step_counter = int(state["common_step_counter"])
+        self.fixed_action_delay = state["fixed_action_delay"]
+        np.random.set_state(state["np_random"])
+        self.extras = {}
+
     def render(self, sync_frame_time=True):
         pass  # headless only (viewer is out of scope, SURVEY section 2 #20)
 

@@ -174,6 +174,21 @@ class PPO:
         chip idle at 4096 envs).  process_env_step() waits for the critic before it stores the transition.  The outputs are
         consumed (env.step, the storage kernel) before the next call overwrites them.  The sampling draws from torch's default
         generator, which CUDA graphs advance per replay."""
+        self._ensure_act_graph(actor_observations, critic_observations)
+        cur = torch.cuda.current_stream(self.device)
+        self._ev_obs.record(cur)                       # this step's observations are final on the current stream
+        self._act_side.wait_event(self._ev_obs)
+        with torch.cuda.stream(self._act_side):
+            self._act_in[1].copy_(critic_observations)
+            self._critic_graph.replay()
+            self._ev_critic.record(self._act_side)
+        self._critic_pending = True
+        self._act_in[0].copy_(actor_observations)
+        self._act_graph.replay()
+        return self._act_out
+
+    def _ensure_act_graph(self, actor_observations, critic_observations):
+        """Capture the two policy-step graphs of _act_graphed for these observation shapes, unless they exist already."""
         key = (tuple(actor_observations.shape), tuple(critic_observations.shape))
         ac = self.actor_critic
         cur = torch.cuda.current_stream(self.device)
@@ -221,16 +236,6 @@ class PPO:
                 self._act_out = (a_out[0], v_out, a_out[1], a_out[2], a_out[3])
                 self._ev_obs, self._ev_critic = torch.cuda.Event(), torch.cuda.Event()
             self._act_key = key
-        self._ev_obs.record(cur)                       # this step's observations are final on the current stream
-        self._act_side.wait_event(self._ev_obs)
-        with torch.cuda.stream(self._act_side):
-            self._act_in[1].copy_(critic_observations)
-            self._critic_graph.replay()
-            self._ev_critic.record(self._act_side)
-        self._critic_pending = True
-        self._act_in[0].copy_(actor_observations)
-        self._act_graph.replay()
-        return self._act_out
 
     def _join_critic(self):
         """values of the current policy step are ready on the current stream from here on"""
@@ -634,14 +639,19 @@ class PPO:
             for k, v in sv.items():
                 stt[k].copy_(v)
 
-    def _update_graphed(self):
+    def _ensure_update_graph(self):
         st = self.storage
-        batch = st.num_envs * st.num_transitions_per_env
-        mb = batch // self.num_mini_batches
+        mb = st.num_envs * st.num_transitions_per_env // self.num_mini_batches
         if self._graph is None or self._graph_mb != mb:
             # capture after the optimizer already ran (resume / later iterations): keep its moments
             self._restore_opt = self._opt_tensors() if len(self.optimizer.state) else None
-            self._build_graph(mb)
+            with self._blas_for_update():
+                self._build_graph(mb)
+        return mb
+
+    def _update_graphed(self):
+        mb = self._ensure_update_graph()
+        st = self.storage
         flat = lambda x: x.flatten(0, 1)
         cobs = st.pri_observations if st.pri_observations is not None else st.observations
         srcs = [flat(x) for x in (st.observations, cobs, st.actions, st.values, st.advantages, st.returns, st.actions_log_prob, st.mu, st.sigma)]
@@ -703,6 +713,32 @@ class PPO:
         else:
             self.learning_rate = float(self.optimizer.param_groups[0]["lr"])
         self.invalidate_graphs()
+
+    def prepare_graphs(self, actor_observations, critic_observations):
+        """Capture now the graphs act() and update() would capture on first use.  Their warm-up runs draw from torch's CUDA generator
+        (the policy's action noise); an exact resume captures them first and sets the generator to the saved state afterwards
+        (OnPolicyRunner.load_train_state)."""
+        if self._use_act_graph and actor_observations.is_cuda:
+            self._ensure_act_graph(actor_observations, critic_observations)
+        if self._use_graph and self.storage is not None:
+            self._ensure_update_graph()
+
+    def get_train_state(self):
+        """What update() carries from one iteration to the next besides parameters and Adam state: the adaptive learning rate
+        (host value and the device scalar Adam reads), the last mean KL and the precision."""
+        return {"learning_rate": float(self.learning_rate), "mean_kl": float(self.mean_kl), "precision": self.precision,
+                "lr_t": self._lr_t.detach().cpu().clone() if self._device_lr else None}
+
+    def set_train_state(self, state):
+        if state["precision"] != self.precision:
+            raise ValueError(f"PPO: the training state was saved with precision={state['precision']!r}, this PPO runs {self.precision!r}")
+        self.learning_rate, self.mean_kl = state["learning_rate"], state["mean_kl"]
+        if self._device_lr:
+            with torch.no_grad():
+                self._lr_t.copy_(state["lr_t"].to(self._lr_t.device))   # (in place: Adam's param group and captured graphs read this tensor)
+        else:
+            for g in self.optimizer.param_groups:
+                g["lr"] = self.learning_rate
 
     def invalidate_graphs(self):
         """captured policy / minibatch graphs refer to the tensors they were captured with: recapture on next use"""

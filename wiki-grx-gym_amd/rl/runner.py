@@ -10,6 +10,7 @@ once per iteration; TensorBoard is optional (a JSON-lines scalar log is always w
 torch.distributed initialised only rank 0 logs and saves."""
 import json
 import os
+import random
 import statistics
 import time
 from collections import deque
@@ -57,6 +58,14 @@ class OnPolicyRunner:
         self.algorithm = _ALGORITHMS[self.cfg["algorithm_class_name"]](actor_critic=actor_critic, device=device, **self.algorithm_cfg)
         self.alg = self.algorithm
         self.num_steps_per_env, self.save_interval = self.cfg["num_steps_per_env"], self.cfg["save_interval"]
+        # exact resume: every save() also writes train_state_<it>.pt, the whole training state; not a config key
+        # (`--exact_resume` or an assignment to train_cfg.runner sets it)
+        self.exact_resume = bool(self.cfg.get("exact_resume", False))
+        if self.exact_resume and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("exact_resume: one process only (with more ranks every rank holds its own env shard)")
+        self._pending_state = None   # what load_train_state() restored and learn() still has to apply
+        self._log_buffers = None     # learn()'s running episode reward / length and the finished episodes' deques
+        self._next_iteration = None  # the iteration a save() from inside learn() resumes at
         self.algorithm.init_storage(env.num_envs, self.num_steps_per_env)
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             torch.manual_seed(int(train_cfg.get("seed", 1)) + 1000 * dist.get_rank())   # different action noise per shard
@@ -75,7 +84,8 @@ class OnPolicyRunner:
         env, alg = self.env, self.algorithm
         if self.log_dir is not None and self.writer is None and self.is_main:
             self.writer = _ScalarLog(self.log_dir)
-        if init_at_random_ep_len:
+        pending, self._pending_state = self._pending_state, None
+        if init_at_random_ep_len and pending is None:   # (an exact resume continues the saved episodes)
             env.episode_length_buf = torch.randint_like(env.episode_length_buf, high=int(env.max_episode_length))
         obs = env.get_observations()
         pri = env.get_privileged_observations()
@@ -83,9 +93,18 @@ class OnPolicyRunner:
         obs, critic_obs = obs.to(self.device), critic_obs.to(self.device)
         alg.actor_critic.train()
         ep_infos = []
-        rewbuffer, lenbuffer = deque(maxlen=100), deque(maxlen=100)
-        cur_rew = torch.zeros(env.num_envs, dtype=torch.float, device=self.device)
-        cur_len = torch.zeros(env.num_envs, dtype=torch.float, device=self.device)
+        if pending is None:
+            rewbuffer, lenbuffer = deque(maxlen=100), deque(maxlen=100)
+            cur_rew = torch.zeros(env.num_envs, dtype=torch.float, device=self.device)
+            cur_len = torch.zeros(env.num_envs, dtype=torch.float, device=self.device)
+        else:
+            rewbuffer, lenbuffer = deque(pending["rewbuffer"], maxlen=100), deque(pending["lenbuffer"], maxlen=100)
+            cur_rew, cur_len = pending["cur_rew"].to(self.device), pending["cur_len"].to(self.device)
+            # the uninterrupted run captured its graphs at iteration 0, and their warm-up runs drew from the CUDA generator: capture them
+            # here, then continue every generator from where the saved run left it
+            alg.prepare_graphs(obs, critic_obs)
+            self._set_rng_state(pending["rng"])
+        self._log_buffers = (cur_rew, cur_len, rewbuffer, lenbuffer)
         done_rew = torch.zeros(self.num_steps_per_env, env.num_envs, dtype=torch.float, device=self.device)
         done_len = torch.zeros(self.num_steps_per_env, env.num_envs, dtype=torch.float, device=self.device)
         tot_iter = self.current_learning_iteration + num_learning_iterations
@@ -123,11 +142,14 @@ class OnPolicyRunner:
             if self.log_dir is not None and self.is_main:
                 self.log(locals())
             if self.log_dir is not None and self.is_main and it % self.save_interval == 0:
+                self._next_iteration = it + 1
                 self.save(os.path.join(self.log_dir, f"model_{it}.pt"))
             ep_infos.clear()
         self.current_learning_iteration += num_learning_iterations
         if self.log_dir is not None and self.is_main:
+            self._next_iteration = self.current_learning_iteration
             self.save(os.path.join(self.log_dir, f"model_{self.current_learning_iteration}.pt"))
+        self._next_iteration = None
 
     def log(self, locs, width=80, pad=35):
         it = locs["it"]
@@ -175,6 +197,52 @@ class OnPolicyRunner:
         torch.save({"model_state_dict": self.algorithm.actor_critic.state_dict(),
                     "optimizer_state_dict": self.algorithm.optimizer.state_dict(),
                     "iter": self.current_learning_iteration, "infos": infos}, path)
+        if self.exact_resume:
+            torch.save(self._train_state(), train_state_path(path))
+
+    def _train_state(self):
+        """train_state_<it>.pt: everything besides model_<it>.pt that the run's next iteration depends on"""
+        dev = torch.device(self.device)
+        cur_rew, cur_len, rewbuffer, lenbuffer = self._log_buffers if self._log_buffers is not None else (None, None, [], [])
+        return {
+            "format": 1,
+            "next_iteration": self._next_iteration if self._next_iteration is not None else self.current_learning_iteration,
+            "env": self.env.get_state(),
+            "alg": self.algorithm.get_train_state(),
+            "rng": {"torch_cpu": torch.get_rng_state(), "torch_cuda": torch.cuda.get_rng_state(dev) if dev.type == "cuda" else None,
+                    "python": random.getstate()},
+            "runner": {"tot_timesteps": self.tot_timesteps, "tot_time": self.tot_time,
+                       "cur_rew": cur_rew.cpu() if cur_rew is not None else None, "cur_len": cur_len.cpu() if cur_len is not None else None,
+                       "rewbuffer": list(rewbuffer), "lenbuffer": list(lenbuffer)},
+        }
+
+    def _set_rng_state(self, rng):
+        torch.set_rng_state(rng["torch_cpu"])
+        if rng["torch_cuda"] is not None:
+            torch.cuda.set_rng_state(rng["torch_cuda"], torch.device(self.device))
+        random.setstate(rng["python"])
+
+    def load_train_state(self, model_path):
+        """Exact resume from the train_state_<it>.pt next to model_<it>.pt (load(model_path) first): env, learning rate, iteration
+        counter and logging state now; the random generators when learn() has captured its graphs.  Raises if the file is missing."""
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("exact_resume: one process only (with more ranks every rank holds its own env shard)")
+        path = train_state_path(model_path)
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"exact resume: {path} is missing (the run was not saved with exact_resume)")
+        state = torch.load(path, map_location="cpu", weights_only=False)
+        self.env.set_state(state["env"])
+        # the parameters exactly as saved: load() keeps the reference's reset of `std` to set_noise_std (actor_critic_mlp.py:116-134)
+        saved = torch.load(model_path, map_location=self.device, weights_only=False)["model_state_dict"]
+        torch.nn.Module.load_state_dict(self.algorithm.actor_critic, saved)
+        self.algorithm.set_train_state(state["alg"])
+        self.current_learning_iteration = state["next_iteration"]
+        r = state["runner"]
+        self.tot_timesteps, self.tot_time = r["tot_timesteps"], r["tot_time"]
+        zeros = torch.zeros(self.env.num_envs, dtype=torch.float)
+        self._pending_state = {"rng": state["rng"], "rewbuffer": r["rewbuffer"], "lenbuffer": r["lenbuffer"],
+                               "cur_rew": r["cur_rew"] if r["cur_rew"] is not None else zeros, "cur_len": r["cur_len"] if r["cur_len"] is not None else zeros}
+        return state
 
     def load(self, path, load_optimizer=True):
         loaded = torch.load(path, map_location=self.device, weights_only=False)
@@ -190,3 +258,9 @@ class OnPolicyRunner:
         if device is not None:
             self.algorithm.actor_critic.to(device)
         return self.algorithm.actor_critic.act_inference
+
+
+def train_state_path(model_path):
+    """train_state_<it>.pt next to model_<it>.pt (no "model" in the name: get_load_path picks the last file containing it)"""
+    d, name = os.path.split(model_path)
+    return os.path.join(d, "train_state_" + name[len("model_"):] if name.startswith("model_") else "train_state_" + name)

@@ -275,6 +275,29 @@ class SimHandle:
         return {"lanes_per_env": int(li.lanes_per_env), "waves_per_block": int(li.waves_per_block), "envs_per_block": int(li.envs_per_block),
                 "num_blocks": int(li.num_blocks), "kernel": li.kernel.decode()}
 
+    def state_bytes(self):
+        """Size of this handle's snapshot (include/grx.h grx_state_bytes)."""
+        v = C.c_int64(0)
+        self._check(self._api["state_bytes"](self._h, C.byref(v)), "state_bytes")
+        return int(v.value)
+
+    def save_state(self):
+        """The handle's mutable state as bytes (include/grx.h grx_save_state; synchronises the current stream)."""
+        if "save_state" not in self._api:
+            raise GrxError("this backend has no grx_save_state")
+        n = self.state_bytes()
+        buf = np.empty(n, dtype=np.uint8)
+        self._check(self._api["save_state"](self._h, buf.ctypes.data, n, self._stream()), "save_state")
+        return buf.tobytes()
+
+    def load_state(self, blob):
+        """Restore a snapshot of save_state() (include/grx.h grx_load_state): raises, with the handle unchanged, when the blob was written
+        by a handle created from other inputs."""
+        if "load_state" not in self._api:
+            raise GrxError("this backend has no grx_load_state")
+        buf = np.frombuffer(bytes(blob), dtype=np.uint8)
+        self._check(self._api["load_state"](self._h, buf.ctypes.data, int(buf.size), self._stream()), "load_state")
+
     def close(self):
         if self._h:
             self._views.clear()

@@ -58,6 +58,8 @@ def get_args(argv=None):
     p.add_argument("--terrain", type=str, choices=["plane", "heightfield", "trimesh"], help="override cfg.terrain.mesh_type")
     p.add_argument("--precision", type=str, choices=["fp32", "bf16"],
                    help="PPO's hidden-layer matrix products: fp32 (default) or bf16 operands with fp32 accumulation (HIP only)")
+    p.add_argument("--exact_resume", action="store_true", default=False,
+                   help="Every checkpoint also saves the whole training state (train_state_<it>.pt); with --resume, continue from it bit for bit")
     args = p.parse_args(argv)
     args.sim_device_type, args.compute_device_id = parse_device_str(args.sim_device)
     args.use_gpu_pipeline = args.pipeline.lower() in ("gpu", "cuda")
@@ -90,6 +92,8 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
                 setattr(cfg_train.runner, name, getattr(args, name))
         if getattr(args, "precision", None) is not None:   # (only when given: the algorithm config has no such key otherwise)
             cfg_train.algorithm.precision = args.precision
+        if getattr(args, "exact_resume", False):   # (likewise: the runner config has no such key otherwise)
+            cfg_train.runner.exact_resume = True
     return env_cfg, cfg_train
 
 

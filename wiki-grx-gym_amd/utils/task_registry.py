@@ -83,6 +83,8 @@ class TaskRegistry:
             resume_path = get_load_path(log_root, load_run=train_cfg.runner.load_run, checkpoint=train_cfg.runner.checkpoint)
             print(f"Loading model from: {resume_path}")
             runner.load(resume_path)
+            if getattr(train_cfg.runner, "exact_resume", False):
+                runner.load_train_state(resume_path)
         return runner, train_cfg
 
 
