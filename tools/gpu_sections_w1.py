@@ -22,10 +22,10 @@ for terrain in ("plane", "heightfield"):
     acts = [random_actions(cfg, N, gen, 1.0).cuda() for _ in range(4)]
     for i in range(int(os.environ.get("STEPS", 200))): s.step(acts[i % 4], 5.0, i + 1)
     torch.cuda.synchronize()
-    lib = C.CDLL(PROF); nbmax = N // 32; buf = (C.c_longlong * (nbmax * 96))()
+    lib = C.CDLL(PROF); nbmax = N // 32; buf = (C.c_longlong * (nbmax * 192))()
     lib.grx_debug_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     nb = lib.grx_debug_profile(s._h, buf, nbmax)
-    full = np.array(buf[:], dtype=np.int64).reshape(nbmax, 96)[:nb]
+    full = np.array(buf[:], dtype=np.int64).reshape(nbmax, 192)[:nb]
     a = full[:, :11]
     d = np.diff(a, axis=1)
     tot = a[:, 10] - a[:, 0]

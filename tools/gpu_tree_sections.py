@@ -19,10 +19,10 @@ for terrain in ("plane", "heightfield"):
     acts = [random_actions(cfg, N, gen, 0.3).cuda() for _ in range(4)]
     for i in range(40): s.step(acts[i % 4], 5.0, i + 1)
     torch.cuda.synchronize()
-    lib = C.CDLL(PROF); buf = (C.c_longlong * (64 * 96))()
+    lib = C.CDLL(PROF); buf = (C.c_longlong * (64 * 192))()
     lib.grx_debug_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     nb = lib.grx_debug_profile(s._h, buf, 64)
-    full = np.array(buf[:], dtype=np.int64).reshape(64, 96)[:nb]
+    full = np.array(buf[:], dtype=np.int64).reshape(64, 192)[:nb]
     med = np.median(full[:, :10], axis=0)
     print(terrain, s.layout(), "cycles per policy step (wave 0, median over blocks): physics", int(med[8]), "whole kernel", int(med[9]))
     for n, v in zip(names, med[:8]): print(f"   {n:16s} {v:9.0f}  ({v / 10:7.0f} per sub-step)")

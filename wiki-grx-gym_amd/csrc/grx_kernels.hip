@@ -51,7 +51,10 @@ typedef const GRX_AS4 KParams& KP;
 // sub-step sections accumulate in registers (g_tacc is a kernel-scope local); sched_barrier pins the code motion
 #define GRX_TICKW(i) do { __builtin_amdgcn_sched_barrier(0); long long t_ = clock64(); if ((threadIdx.x & 63) == 0) P.prof[(size_t)blockIdx.x * GRX_PROF_SLOTS + (i)] = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
 #define GRX_TICK2(i) do { __builtin_amdgcn_sched_barrier(0); long long t_ = clock64(); tacc[(i) - 16] += t_ - tprev; tprev = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
+// the tail's per-wave timeline: a stamp in slot base + the wave's role (W == 8: waves 0..7)
+#define GRX_TICKV(base) do { __builtin_amdgcn_sched_barrier(0); long long t_ = clock64(); if ((threadIdx.x & 63) == 0) P.prof[(size_t)blockIdx.x * GRX_PROF_SLOTS + (base) + wv] = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
 #else
+#define GRX_TICKV(base) do {} while (0)
 #define GRX_TICK2(i) do {} while (0)
 #define GRX_TICK(i) do {} while (0)
 #define GRX_TICKW(i) do {} while (0)

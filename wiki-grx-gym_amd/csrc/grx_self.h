@@ -241,10 +241,15 @@ GRX_DEV void self_collision(KP P, const KTables& T, const SideConst& C, const Se
             { const long long t_ = clock64(); pacc[6] += t_ - tp_; tp_ = t_; }   // pair tests
             pacc[2] += __popcll(__ballot(hm != 0ull)); pacc[3] += 1;
 #endif
+            // Lane quads: the two halves of a leg hold the same mask; they take its pairs in turn (even / odd rank in ascending order) and
+            // add their partial sums below, so that a leg pair with n overlapping pairs costs ceil(n / 2) rounds instead of n.  The blocks
+            // whose legs cross are the slowest of a launch, and the launch lasts as long as its slowest block (tools/gpu_sections.py).
+            if (LPL == 2 && hf_) hm &= hm - 1ull;
             while (__any(hm != 0ull)) {   // overlapping pairs of this lane's env, ascending
                 if (hm) {
                     const int pid = __ffsll((long long)hm) - 1;
                     hm &= hm - 1ull;
+                    if (LPL == 2) hm &= hm - 1ull;   // (the other half's)
                     const int sa = pid >> 3, sb_ = pid & 7;      // left shape, right shape
                     const int ms = side == 0 ? sa : sb_, os = side == 0 ? sb_ : sa;   // mine, the other leg's
                     const int kb = ms < 2 ? 0 : (ms < 4 ? 1 : 2), ko = os < 2 ? 0 : (os < 4 ? 1 : 2);   // carrying chain body - 2
@@ -265,6 +270,10 @@ GRX_DEV void self_collision(KP P, const KTables& T, const SideConst& C, const Se
                         else { o.fa[2] = o.fa[2] + Tq; o.fl[2] = o.fl[2] + F; }
                     }
                 }
+            }
+            if (LPL == 2) {   // the two halves' partial sums: the same total on both (and, pair by pair, opposite in the other leg's lanes)
+#pragma unroll
+                for (int i = 0; i < 3; ++i) { o.fa[i] = half_sum(o.fa[i]); o.fl[i] = half_sum(o.fl[i]); }
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the rows are rewritten by the next sub-step
 #ifdef GRX_PROFILE_SECTIONS

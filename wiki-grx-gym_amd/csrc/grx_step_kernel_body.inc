@@ -53,6 +53,9 @@
     __shared__ int s_flag[FL_COUNT];
     const PipeLds L = {s_bq, s_q, s_wc, s_pb, reinterpret_cast<float4*>(s_wr), s_flag, s_xk, s_sb, s_fx};
     const int tid = threadIdx.x;
+#ifdef GRX_PROFILE_SECTIONS   // the block's first instruction, as wall time (100 MHz: comparable across blocks) and as cycles
+    if (tid == 0) { P.prof[(size_t)blockIdx.x * GRX_PROF_SLOTS + 136] = (long long)__builtin_amdgcn_s_memrealtime(); P.prof[(size_t)blockIdx.x * GRX_PROF_SLOTS + 137] = clock64(); }
+#endif
 #ifndef GRX_W8_ROLES
 #define GRX_W8_ROLES 0x76543210u   // role of hardware wave i in nibble i (waves i and i + 4 share a SIMD: pair a busy role with a light one)
 #endif
@@ -193,7 +196,7 @@
                 // FL_SCAN instead of a block barrier.
                 if (W == 8) { if (wv != 3) { s_hsum[wv * 64 + lane] = height_scan_share<6, (LPE == 4 ? 6 : 11)>(P, s_tab, hp[2 * EPB], hp[3 * EPB], v3(hp[0 * EPB], hp[1 * EPB], 0.f),
                                                                                            LPE * (wv < 3 ? wv - 1 : wv - 2) + (lane & (LPE - 1)), nh, s_pri + el * PRS);
-                                             flag_add(s_flag + FL_SCAN, lane); } }
+                                             flag_add(s_flag + FL_SCAN, lane); GRX_TICKV(96); } }
                 else {
                 s_hsum[wv * 64 + lane] = height_scan_share<4>(P, s_tab, hp[2 * EPB], hp[3 * EPB], v3(hp[0 * EPB], hp[1 * EPB], 0.f),
                                                               LPE * wv + (lane & (LPE - 1)), nh, s_pri + el * PRS);
@@ -209,6 +212,7 @@
                 z[3 * 64] = f4(rr.root[7], rr.root[8], rr.cmd[0], rr.cmd[1]);
                 z[4 * 64] = f4(rr.cmd[2], 0.f, 0.f, 0.f);
                 flag_set(s_flag + FL_RR, 1, lane);
+                GRX_TICKV(104);
             }
             if (wv == 3) {   // the base / feet half of the reward terms, then half of the observation height block
                 flag_wait(s_flag + FL_REW, 1);
@@ -218,6 +222,7 @@
                 if (W == 8 && HF) rin.feet_height = scan_feet_height(P, s_flag, s_hsum, rin.feet_height, nh, lane);
                 reward_and_sums<2>(P, C, rin, lane, side, e, N, act, s_stat, es_w3, s_rwp, s_flag + FL_RWB, nullptr,
                                    DBG && dbg[(size_t)DBG_APPLY_RESET * N + e] == 0.f);
+                GRX_TICKV(104);
             }
             if (wv == 1) {   // rewards + episode sums while wave 0 runs reset / observations / stores
                 flag_wait(s_flag + FL_REW, 1);
@@ -234,6 +239,7 @@
                 reward_and_sums<1>(P, C, rin, lane, side, e, N, act, s_stat, es_w1, s_rwp, s_flag + FL_RWB, DBG ? a_ll1 : nullptr,
                                    DBG && dbg[(size_t)DBG_APPLY_RESET * N + e] == 0.f);
                 GRX_TICKW(15);
+                GRX_TICKV(104);
             }
             if (W == 8) {   // eight waves: the observation height block on the four waves that have no reward terms, a quarter each
                 if (wv >= 4) {
@@ -244,6 +250,7 @@
                     if (HF) s_bho[(wv - 4) * 64 + lane] = env_sum(part);
                     else s_hsum[wv * 64 + lane] = env_sum(part);   // (plane: no scan, the rows of waves 4..7 in s_hsum as before)
                     flag_set(s_flag + (wv == 7 ? FL_BHO4 : FL_BHO1 + (wv - 4)), 1, lane);
+                    GRX_TICKV(112);
                 }
             } else if (wv < 4) {   // the observation height block, once wave 0 has published the (post-reset) base height: wave 2 takes
                 // the points k = 0, 1 (mod 4), waves 1 and 3 (busy with the rewards until now) k = 2, 3 and 6, 7 (mod 8)
@@ -770,6 +777,7 @@
     // ---- coalesced AoS output rows (all waves): the block's 32 obs / pri_obs rows are contiguous in HBM
     // (the rows and the statistics are staged in LDS: an LDS-only barrier -- a full one would drain every wave's state stores first,
     //  measured 14 k cycles here)
+    GRX_TICKV(120);
     lds_barrier();
     {
         const int e0 = grp * EPB;
@@ -800,3 +808,7 @@
     //  whole-L2 write-back on this 8-XCD part, +10 us per launch; agent-scope atomics without a fence wait +9 us for the
     //  acknowledgements.  Round 2 paid a 4.5 us kernel of its own per step instead.)
     GRX_TICK(10);
+    GRX_TICKV(128);
+#ifdef GRX_PROFILE_SECTIONS
+    if ((tid & 63) == 0) P.prof[(size_t)blockIdx.x * GRX_PROF_SLOTS + 144 + wv] = (long long)__builtin_amdgcn_s_memrealtime();
+#endif

@@ -51,8 +51,9 @@
 #endif
 
 #ifdef GRX_PROFILE_SECTIONS
-// timeline of sub-step 5: event stamps in slots 48.. of the block's row (tools/gpu_sections.py prints them relative to EV 0)
-#define GRX_EV(i) do { if (seq == 5 && lane == 0) { __builtin_amdgcn_sched_barrier(0); P.prof[(size_t)blockIdx.x * GRX_PROF_SLOTS + 48 + (i)] = clock64(); __builtin_amdgcn_sched_barrier(0); } } while (0)
+// timeline of sub-step 5: event stamps in slots 48.. of the block's row (tools/gpu_sections.py prints them relative to EV 0); the same events
+// of sub-step 0 -- the one that also carries the policy step's once-per-step work -- in slots 160..
+#define GRX_EV(i) do { if ((seq == 5 || seq == 0) && lane == 0) { __builtin_amdgcn_sched_barrier(0); P.prof[(size_t)blockIdx.x * GRX_PROF_SLOTS + (seq == 5 ? 48 : 160) + (i)] = clock64(); __builtin_amdgcn_sched_barrier(0); } } while (0)
 #else
 #define GRX_EV(i) do {} while (0)
 #endif
