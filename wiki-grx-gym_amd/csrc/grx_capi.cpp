@@ -19,49 +19,34 @@
 #include "grx_rng.h"
 
 extern "C" {
-void grx_launch_step(const KParams* dP, int N, int heightfield, int waves, const float* actions, float delay, long long common_step,
-                     const float* noise, float* obs_out, float* pri_out, const StepSeq* sq, hipStream_t stream);
-void grx_launch_step_quad(const KParams* dP, int N, int heightfield, int waves, const float* actions, float delay, long long common_step,
-                          const float* noise, float* obs_out, float* pri_out, const StepSeq* sq, hipStream_t stream);
-int grx_envs_per_block_quad(void);
+// the kernel families' table lookups (grx_device.h, "the step kernels' tables") and, where a kernel's argument types are private to its
+// translation unit, the family's typed launch
+const FusedStepRow* grx_step_row(int terrain, int waves, int base, int dbg, int* envs_per_block);        // lane pairs (grx_kernels.hip)
+const FusedStepRow* grx_step_row_quad(int terrain, int waves, int base, int dbg, int* envs_per_block);   // lane quads (grx_quad.hip)
+int grx_tree_row(int terrain, int base, int waves, int nb, int nlc, int nchain, int nsph, const StepRow** row, const StepRow** dbg_row, int* envs_per_block, int* lds_bytes);
+void grx_launch_step_tree(const StepRow* row, const KParams* dP, const void* tree_tab, const void* gen_tab, int nblocks, int waves, int lds_bytes, const float* actions,
+                          float delay, long long common_step, const float* noise, float* obs_out, float* pri_out, const StepSeq* sq, const float* dbg, hipStream_t stream);
+// csrc/grx_tree16.hip: the tree kernel with a 16-lane group per env (four envs per wave)
+int grx_tree_row16(int terrain, int base, int waves, int nb, int nlc, int nchain, int nsph, const StepRow** row, const StepRow** dbg_row, int* envs_per_block, int* lds_bytes);
+void grx_launch_step_tree16(const StepRow* row, const KParams* dP, const void* tree_tab, const void* gen_tab, int nblocks, int waves, int lds_bytes, const float* actions,
+                            float delay, long long common_step, const float* noise, float* obs_out, float* pri_out, const StepSeq* sq, const float* dbg, hipStream_t stream);
+int grx_generic_row(int terrain, int base, int lds_bytes, const StepRow** row);
+void grx_launch_step_generic(const StepRow* row, const KParams* dP, const void* tables, float* ws, int nblocks, int epb, int lds_bytes, const float* actions, float delay,
+                             long long common_step, const float* noise, float* obs_out, float* pri_out, long long seq, hipStream_t stream);
+void grx_launch_reset_all_generic(const KParams* dP, const void* tables, int nblocks, int epb, uint32_t step, long long seq, uint8_t* mask, hipStream_t stream);
+int grx_generic_tables_size(void);
+int grx_generic_ws_floats_per_env(int nb, int nlc);
 void grx_launch_finalize(const KParams* dP, long long seq, long long* progress, long long ticket, hipStream_t stream);
 void grx_launch_ticket(long long* progress, long long ticket, hipStream_t stream);
-int grx_launch_step_generic(const KParams* dP, const void* tables, float* ws, int N, int epb, int lds_bytes, int heightfield, const float* actions,
-                            float delay, long long common_step, const float* noise, float* obs_out, float* pri_out, long long seq, int base, hipStream_t stream);
-void grx_launch_reset_all_generic(const KParams* dP, const void* tables, int N, int epb, uint32_t step, long long seq, uint8_t* mask, hipStream_t stream);
-int grx_generic_tables_size(void);
-int grx_tree_lds_bytes(int nb, int nlc, int nchain, int nsph, int waves);
-int grx_tree_envs_per_wave(void);
-int grx_launch_step_tree(const KParams* dP, const void* tree_tab, const void* gen_tab, int N, int waves, int lds_bytes, int heightfield, const float* actions, float delay,
-                         long long common_step, const float* noise, float* obs_out, float* pri_out, const StepSeq* sq, int base, hipStream_t stream);
-int grx_launch_step_tree_debug(const KParams* dP, const void* tree_tab, const void* gen_tab, int N, int waves, int lds_bytes, int heightfield, const float* actions,
-                               long long common_step, const float* noise, const float* dbg, const StepSeq* sq, int base, hipStream_t stream);
-int grx_generic_ws_floats_per_env(int nb, int nlc);
-// csrc/grx_tree16.hip: the tree kernel with a 16-lane group per env (four envs per wave)
-int grx_tree_lds_bytes16(int nb, int nlc, int nchain, int nsph, int waves);
-int grx_tree_envs_per_wave16(void);
-int grx_launch_step_tree16(const KParams* dP, const void* tree_tab, const void* gen_tab, int N, int waves, int lds_bytes, int heightfield, const float* actions, float delay,
-                           long long common_step, const float* noise, float* obs_out, float* pri_out, const StepSeq* sq, int base, hipStream_t stream);
-int grx_launch_step_tree_debug16(const KParams* dP, const void* tree_tab, const void* gen_tab, int N, int waves, int lds_bytes, int heightfield, const float* actions,
-                                 long long common_step, const float* noise, const float* dbg, const StepSeq* sq, int base, hipStream_t stream);
 void grx_launch_reset_all(const KParams* dP, int N, uint32_t step, const StepSeq* sq, uint8_t* mask, hipStream_t stream);
 void grx_launch_mark(const int32_t* env_ids, int n, int N, uint8_t* mask, hipStream_t stream);
 void grx_launch_set_state(const KParams* dP, int N, const float* root, const float* q, const float* qd, const int32_t* env_ids, int n, hipStream_t stream);
-int grx_envs_per_block(void);
 void grx_launch_refresh_heights(const KParams* dP, int N, int nh, hipStream_t stream);
 void grx_launch_debug_terrain(const KParams* dP, const float* xy, int n, float* out, hipStream_t stream);
 void grx_launch_debug_wall(const KParams* dP, const float* xyzr, int n, float* out, hipStream_t stream);
 void grx_launch_refresh_rbs(const KParams* dP, int N, int nlinks, int pushed, hipStream_t stream);
-void grx_launch_step_debug(const KParams* dP, int N, int heightfield, int waves, const float* actions, long long common_step, const float* noise,
-                           const float* dbg, const StepSeq* sq, hipStream_t stream);
-void grx_launch_step_debug_quad(const KParams* dP, int N, int heightfield, int waves, const float* actions, long long common_step, const float* noise,
-                                const float* dbg, const StepSeq* sq, hipStream_t stream);
 int grx_debug_rows(void);
-// ABI 7: the one-wave entries with legged_gym's base reward terms and their statistics kernels
-void grx_launch_step_base(const KParams* dP, int N, int heightfield, const float* actions, float delay, long long common_step,
-                          const float* noise, float* obs_out, float* pri_out, const StepSeq* sq, hipStream_t stream);
-void grx_launch_step_debug_base(const KParams* dP, int N, int heightfield, const float* actions, long long common_step, const float* noise,
-                                const float* dbg, const StepSeq* sq, hipStream_t stream);
+// ABI 7: the statistics kernels of legged_gym's base reward terms
 void grx_launch_base_reset(const KParams* dP, int N, const uint8_t* mask, hipStream_t stream);
 void grx_launch_base_stats(const KParams* dP, long long seq, int nb, hipStream_t stream);
 void grx_launch_curriculum(const KParams* dP, int nb, uint32_t step, float* obs, int nobs, float* pri, int npri, hipStream_t stream);
@@ -112,24 +97,36 @@ struct Pace {
     int64_t issued = 0;                     // ticket of the last step enqueued
     hipStream_t last_stream = nullptr;      // stream of the last ticketed launch (grx_wait_idle sends the closing ticket there)
 };
+
+// The layout a handle steps with, resolved ONCE by plan_layout (grx_create): grx_step, grx_reset_*, grx_debug_post_physics, grx_layout and
+// state_fingerprint only read it.
+enum StepFamily { FAM_PAIR, FAM_QUAD, FAM_TREE, FAM_GENERIC };   // (FAM_TREE: grx_tree.h's 8-lane groups or grx_tree16.hip's 16, by lanes_per_env)
+struct StepPlan {
+    StepFamily family = FAM_PAIR;
+    const StepRow* row = nullptr;    // the family's table rows: the product kernel (its name is what grx_layout reports) ...
+    const StepRow* dbg_row = nullptr;   // ... and the DBG instantiation grx_debug_post_physics launches (the generic family has none)
+    bool base = false;               // ABI 7: legged_gym's base reward terms active -- the *_base entries of the layout
+    int grid = 0, block = 0, dbg_block = 0, lds = 0;   // blocks, threads per block (of the DBG twin's launch: dbg_block), bytes of dynamic LDS
+    int lanes_per_env = 2, waves = 1, envs_per_block = 0;
+    int stat_cols = 0;               // statistics columns a launch of the base terms writes: one per wave of the step kernel
+    // every family's picks as plan_layout made them -- those of the families this handle does not launch too: the snapshot fingerprint hashes them all
+    int fused_waves = 1;             // waves per 32-env block of the lane-pair kernels (1, 2, 4 or 8), or per 16-env block of the lane-quad ones (4 or 8)
+    int tree_g = GRX_TREE_G;         // lanes per env of the tree kernel: 8, or 16 (grx_tree16.hip) while 16-lane groups still fit the SIMDs in one round
+    int tree_waves = 2;              // 8-env waves per block of the tree kernel: 2 while those blocks fit the CUs in one round, else 4 (a whole CU's LDS)
+    int gen_epb = 64, gen_lds = 0;   // generic kernel: envs per (single-wave) block; bytes of dynamic LDS when the workspace lives there (0: global memory)
+    bool generic() const { return family == FAM_TREE || family == FAM_GENERIC; }   // model outside the fast kernel's lower-limb topology (grx_generic.h, grx_tree.h)
+};
 }  // namespace
 
 struct grx_sim {
     grx_config cfg;
     int device = 0;
     int N = 0;
-    int waves = 1;         // waves per 32-env block of the step kernel (1, 2 or 4)
-    bool quad = false;     // four waves, a lane quad per env, 16 envs per block (grx_quad.hip): while the blocks fit the CUs in one round
-    bool generic = false;  // model outside the fast kernel's lower-limb topology: generic-tree kernel (grx_generic.h)
-    bool base = false;     // ABI 7: legged_gym's base reward terms active -- the *_base entries of the layout
-    int base_cols = 0;     // ... their statistics columns per launch: one per wave of the step kernel
+    StepPlan plan;         // which step kernel this handle launches and how
     int rbs_mode = GRX_PUBLISH_NEVER, heights_mode = GRX_PUBLISH_EVERY_STEP;   // grx_publish_mode of GRX_T_RIGID_BODY_STATES / GRX_T_MEASURED_HEIGHTS
     int nd = GRX_ND;
     void* d_gen = nullptr; // GenTables (device)
     void* d_tree = nullptr; // TreeTab (device): the lane-group tree kernel (grx_tree.h) runs this model
-    int tree_lds = 0;      // its dynamic LDS
-    int tree_g = GRX_TREE_G;   // lanes per env of the tree kernel this handle launches: 8, or 16 (grx_tree16.hip) while 16-lane groups still fit the SIMDs in one round
-    int tree_waves = 2;    // 8-env waves per block of the tree kernel: 2 while those blocks fit the CUs in one round, else 4 (a whole CU's LDS)
     float* d_ws = nullptr; // generic workspace
     int64_t seq = 0;       // launches of this handle that write statistics rows (steps, resets, debug steps; recorded ones too)
     int64_t eager_seq = 0; // ... the last of them that was launched eagerly (its rows are what grx_flush_stats reduces)
@@ -141,8 +138,6 @@ struct grx_sim {
     bool last_pushed = false;    // the last step was a _push_robots step (the base's vx, vy were overwritten after the sub-steps)
     bool prev_recorded = false;  // the last launch in host order was recorded into a graph: its successor must not fold "launch seq - 1"
     uint8_t* d_mask = nullptr;   // grx_reset_idx: per-env flags
-    int gen_epb = 64;      // generic kernel: envs per (single-wave) block
-    int gen_lds = 0;       // generic kernel: bytes of dynamic LDS when the workspace lives there (0: global memory)
     KParams hp;            // launch parameters: host image ...
     KParams* d_hp = nullptr;   // ... and the device copy every kernel reads through the constant address space
     KTables tab;           // host image of the device tables
@@ -596,7 +591,9 @@ struct GenTablesH {
     int32_t lc_begin[GEN_MAXLC_H + 1];
 };
 
-int build_generic(grx_sim* s, const grx_config& c) {
+// The generic path's tables: GenTables (device, s->d_gen) with the workspace, and -- G > 0 -- the tree kernel's TreeTab for G lanes per env into
+// `tree` (host; left empty when the model does not fit a lane group: the one-lane generic kernel runs it)
+int build_generic(grx_sim* s, const grx_config& c, int G, std::vector<TreeTab>& tree) {
     const grx_model& m = c.model;
     if ((int)sizeof(GenTablesH) != grx_generic_tables_size()) return fail(GRX_ERR_HIP, "GenTables layout mismatch between grx_capi.cpp and grx_generic.h");
     if (m.num_spheres > GRX_MAX_SPHERES) return fail(GRX_ERR_UNSUPPORTED_MODEL, "too many collision spheres");
@@ -704,20 +701,11 @@ int build_generic(grx_sim* s, const grx_config& c) {
     rc = dalloc(s, &s->d_ws, s->ws_floats);
     if (rc) return rc;
     // ---- the lane-group tree kernel (grx_tree.h): chains of the tree -> lanes, depth levels -> steps
-    if (const char* tv_ = getenv("GRX_TREE")) if (atoi(tv_) == 0) return GRX_OK;
+    if (G <= 0) return GRX_OK;
     std::vector<TreeTab> tt(1);
     TreeTab& K = tt[0];
     memset(&K, 0, sizeof K);
-    // lanes per env: 8 (eight envs per wave), or 16 (four envs per wave: the passes are bound by the tree's depth levels whatever the group
-    // size, but twice the waves) while those waves still have a SIMD each -- 4096 envs on an MI355X, BASELINE.json config 5's per-GPU size
-    int G = GRX_TREE_G;
-    {
-        hipDeviceProp_t prop;
-        HIP_TRY(hipGetDeviceProperties(&prop, s->device));
-        if ((long long)s->N * GRX_TREE_GMAX <= 64ll * 4 * prop.multiProcessorCount) G = GRX_TREE_GMAX;
-        if (const char* g_ = getenv("GRX_TREE_G")) { const int v = atoi(g_); if (v == GRX_TREE_G || v == GRX_TREE_GMAX) G = v; }
-    }
-    K.g = G; s->tree_g = G;
+    K.g = G;
     K.nb = T.nb; K.nd = T.nd; K.nsph = T.nsph; K.nlc = T.nlc;
     memset(K.sched, 0xff, sizeof K.sched);
     std::vector<int> depth(T.nb, -1), lane_of(T.nb, -1), cont(T.nb, 0);
@@ -822,24 +810,104 @@ int build_generic(grx_sim* s, const grx_config& c) {
         for (int k = K.nsp; k < K.nsp_batches * 4 * G; ++k) { K.sp[k].ab = 0u; K.sp[k].r2 = -1.f; }
     }
     for (int l = 0; l <= GEN_MAXLC_H; ++l) K.lc_begin[l] = T.lc_begin[l];
-    // waves per block: two while those blocks fit the device's CUs in one round (every wave still has a SIMD to itself and the CU's
-    // LDS bandwidth is shared by two), else four -- a whole CU's LDS, one wave on every SIMD.  GRX_TREE_WAVES overrides (A/B runs).
-    {
-        hipDeviceProp_t prop;
-        HIP_TRY(hipGetDeviceProperties(&prop, s->device));
-        const int epw = G == GRX_TREE_GMAX ? grx_tree_envs_per_wave16() : grx_tree_envs_per_wave();
-        s->tree_waves = (s->N + 2 * epw - 1) / (2 * epw) <= prop.multiProcessorCount ? 2 : 4;
-        if (const char* tw_ = getenv("GRX_TREE_WAVES")) { const int v = atoi(tw_); if (v == 1 || v == 2 || v == 4) s->tree_waves = v; }
+    tree.swap(tt);
+    return GRX_OK;
+}
+
+// Which step kernel the handle launches, and how: ALL of the layout policy, device properties read once.  generic: the model is outside the
+// fused kernels' lower-limb topology (grx_create); a generic model's tables are built and uploaded on the way (the tree kernel takes a model
+// only if its tables fit a lane group).  A key without a row in its family's table is refused here, not at launch time.
+int plan_layout(grx_sim* s, const grx_config& c, bool generic, bool base) {
+    StepPlan& L = s->plan;
+    const int N = c.num_envs;
+    // the tables' terrain key: 0 plane, 1 the raster as a heightfield, 2 mesh_type 'trimesh' (the *_trimesh kernels: the reference's corrected mesh)
+    const int terrain = c.terrain_type == GRX_TERRAIN_HEIGHTFIELD ? (c.vertical_faces ? 2 : 1) : 0;
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, s->device));
+    L.base = base;
+    bool quad = false;     // four waves, a lane quad per env, 16 envs per block (grx_quad.hip): while the blocks fit the CUs in one round
+    int pair_epb = 0, quad_epb = 0;
+    grx_step_row(terrain, 1, 0, 0, &pair_epb); grx_step_row_quad(terrain, 8, 0, 0, &quad_epb);
+    const int nblocks = (N + pair_epb - 1) / pair_epb;
+    {   // waves per block: the step kernel needs a SIMD per wave (512 registers/lane).  Four waves per block while the
+        // blocks fit the device's SIMDs in at most TWO rounds (measured on MI355X, rough terrain: 16384 envs = 2 rounds of
+        // the four-wave layout 131 us, two-wave layout 152 us, one-wave layout 170 us; 20480 envs: 192 / 276 / 171 us),
+        // one wave per block beyond; the two-wave layout is never the fastest any more (kept: GRX_WAVES_PER_BLOCK, tests)
+        const int simds = prop.multiProcessorCount * 4;
+        L.fused_waves = nblocks * 4 <= 2 * simds ? 8 : 1;   // (the pipeline with eight waves per block, two per SIMD: +3 % over four at 8192 envs, +1 % at 16384)
+        if (const char* w = getenv("GRX_WAVES_PER_BLOCK")) {
+            const int v = atoi(w);
+            if (v == 1 || v == 2 || v == 4 || v == 8) L.fused_waves = v;
+        }
+        // a lane QUAD per env, 16 envs per block: one block per CU needs all of the CU (four SIMDs' registers, 100+ KB of LDS),
+        // so this layout pays exactly while its blocks fit the device in ONE round -- half the CUs would otherwise idle
+        const int qblocks = (N + quad_epb - 1) / quad_epb;
+        quad = !generic && L.fused_waves >= 4 && qblocks <= prop.multiProcessorCount && !getenv("GRX_WAVES_PER_BLOCK");
+        if (const char* q = getenv("GRX_LANES_PER_ENV")) quad = !generic && atoi(q) == 4;   // tests / A-B runs: 2 or 4
+        if (quad) { L.fused_waves = 8; if (const char* w = getenv("GRX_QUAD_WAVES")) L.fused_waves = atoi(w) == 4 ? 4 : 8; }   // eight waves (two per SIMD) unless a test asks for the four-role pipeline
+        // control_type 'V' / 'T' and heading_command (ABI 5; off in every registered task) live in the general one-wave layout only:
+        // the wave pipelines keep the registered tasks' code path
+        if (c.control_type != GRX_CONTROL_P || c.heading_command) { quad = false; L.fused_waves = 1; }
+        // so do legged_gym's base reward terms (ABI 7), in entries of their own
+        if (base) { quad = false; L.fused_waves = 1; }
     }
-    auto lds_of = [&](int waves) { return G == GRX_TREE_GMAX ? grx_tree_lds_bytes16(T.nb, T.nlc, nchain, T.nsph, waves) : grx_tree_lds_bytes(T.nb, T.nlc, nchain, T.nsph, waves); };
-    int lds = lds_of(s->tree_waves);
-    while (lds > 160 * 1024 - 1024 && s->tree_waves > 1) { s->tree_waves /= 2; lds = lds_of(s->tree_waves); }
-    if (lds > 160 * 1024 - 1024) return GRX_OK;   // the workspace of one wave does not fit a CU's LDS
-    TreeTab* dk = nullptr;
-    rc = dalloc(s, &dk, 1);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(dk, &K, sizeof K, hipMemcpyHostToDevice));
-    s->d_tree = dk; s->tree_lds = lds;
+    if (!generic) {
+        L.family = quad ? FAM_QUAD : FAM_PAIR; L.lanes_per_env = quad ? 4 : 2; L.waves = L.fused_waves;
+        L.row = (quad ? grx_step_row_quad : grx_step_row)(terrain, L.waves, base, 0, &L.envs_per_block);
+        L.dbg_row = (quad ? grx_step_row_quad : grx_step_row)(terrain, L.waves, base, 1, &L.envs_per_block);
+        L.stat_cols = nblocks;   // (the fused one-wave entry: a wave per 32-env block)
+    } else {
+        // generic kernel: the per-body workspace goes to LDS when 16 envs' rows fit (155 KB for the 33-body robot: LDS round
+        // trips are ~5x shorter than global ones and the kernel is bound by exactly those); else 64 envs per block over the
+        // global workspace.  GRX_GENERIC_EPB = 16 / 32 / 64 forces a block size over the GLOBAL workspace (A/B runs).
+        const size_t per_env = (size_t)grx_generic_ws_floats_per_env(c.model.num_bodies, 24) * sizeof(float);
+        // one such block fills a CU's LDS, so this only pays while all blocks run in ONE round (<= 16 envs per CU:
+        // 4096 envs on an MI355X; measured 1.9 ms vs 3.2 ms at 4096 envs, but 7.5 ms vs 3.7 ms at 16384)
+        if (per_env * 16 + 1024 <= 159 * 1024 && (N + 15) / 16 <= prop.multiProcessorCount) { L.gen_epb = 16; L.gen_lds = (int)(per_env * 16); }
+        if (const char* ev = getenv("GRX_GENERIC_EPB")) { const int v = atoi(ev); if (v == 16 || v == 32 || v == 64) { L.gen_epb = v; L.gen_lds = 0; } }
+        // the lane-group tree kernel unless GRX_TREE=0.  Lanes per env: 8 (eight envs per wave), or 16 (four envs per wave: the passes are bound by
+        // the tree's depth levels whatever the group size, but twice the waves) while those waves still have a SIMD each -- 4096 envs on an
+        // MI355X, BASELINE.json config 5's per-GPU size
+        const char* tv_ = getenv("GRX_TREE");
+        const bool try_tree = !(tv_ && atoi(tv_) == 0);
+        if (try_tree) {
+            if ((long long)N * GRX_TREE_GMAX <= 64ll * 4 * prop.multiProcessorCount) L.tree_g = GRX_TREE_GMAX;
+            if (const char* g_ = getenv("GRX_TREE_G")) { const int v = atoi(g_); if (v == GRX_TREE_G || v == GRX_TREE_GMAX) L.tree_g = v; }
+        }
+        std::vector<TreeTab> tree;
+        if (int rc = build_generic(s, c, try_tree ? L.tree_g : 0, tree)) return rc;
+        L.family = FAM_GENERIC;
+        if (!tree.empty()) {
+            const TreeTab& K = tree[0];
+            int refused = 0, epb = 0, lds = 0;
+            auto look = [&](int waves) { refused = (K.g == GRX_TREE_GMAX ? grx_tree_row16 : grx_tree_row)(terrain, base, waves, K.nb, K.nlc, K.nchain, K.nsph, &L.row, &L.dbg_row, &epb, &lds); };
+            // waves per block: two while those blocks fit the device's CUs in one round (every wave still has a SIMD to itself and the CU's
+            // LDS bandwidth is shared by two), else four -- a whole CU's LDS, one wave on every SIMD.  GRX_TREE_WAVES overrides (A/B runs).
+            look(2);
+            L.tree_waves = (N + epb - 1) / epb <= prop.multiProcessorCount ? 2 : 4;
+            if (const char* tw_ = getenv("GRX_TREE_WAVES")) { const int v = atoi(tw_); if (v == 1 || v == 2 || v == 4) L.tree_waves = v; }
+            look(L.tree_waves);
+            while (lds > 160 * 1024 - 1024 && L.tree_waves > 1) { L.tree_waves /= 2; look(L.tree_waves); }
+            if (lds <= 160 * 1024 - 1024) {   // (else the workspace of one wave does not fit a CU's LDS)
+                if (refused) return fail(GRX_ERR_HIP, "grx_create: cannot raise the dynamic LDS limit of the tree kernel");
+                TreeTab* dk = nullptr;
+                if (int rc = dalloc(s, &dk, 1)) return rc;
+                HIP_TRY(hipMemcpy(dk, &K, sizeof K, hipMemcpyHostToDevice));
+                s->d_tree = dk;
+                L.family = FAM_TREE; L.lanes_per_env = K.g; L.waves = L.tree_waves; L.envs_per_block = epb; L.lds = lds;
+            }
+        }
+        if (L.family == FAM_GENERIC) {
+            L.dbg_row = nullptr;
+            if (grx_generic_row(terrain, base, L.gen_lds, &L.row)) return fail(GRX_ERR_HIP, "grx_create: cannot raise the dynamic LDS limit of the generic kernel");
+            L.lanes_per_env = 1; L.waves = 1; L.envs_per_block = L.gen_epb; L.lds = L.gen_lds;
+        }
+    }
+    if (!L.row || (!L.dbg_row && L.family != FAM_GENERIC)) return fail(GRX_ERR_UNSUPPORTED_MODEL, "grx_create: no step kernel for this layout (terrain " + std::to_string(terrain) + ", " + std::to_string(L.waves) + " waves per block)");
+    L.grid = (N + L.envs_per_block - 1) / L.envs_per_block;
+    L.block = L.family == FAM_GENERIC ? L.gen_epb : 64 * L.waves;   // (the one-lane kernel: a thread per env)
+    if (L.dbg_row) L.dbg_block = 64 * (L.dbg_row->waves ? L.dbg_row->waves : L.waves);
+    if (generic) L.stat_cols = L.family == FAM_TREE ? L.grid * L.waves : L.grid;
     return GRX_OK;
 }
 }  // namespace
@@ -869,8 +937,9 @@ uint64_t state_fingerprint(grx_sim* s, const grx_config& c) {
     grx_layout_info li;
     if (grx_layout(s, &li) == GRX_OK) h = fnv1a(h, &li, sizeof li);
     const KParams& P = s->hp;
-    for (int32_t v : {s->N, s->nd, (int)s->generic, (int)s->quad, (int)s->base, s->base_cols, s->waves, s->tree_g, s->tree_waves, s->gen_epb, s->gen_lds,
-                      (int)(s->d_tree != nullptr), s->rbs_mode, s->heights_mode, P.self_collisions, P.publish_debug, P.publish_rbs, P.publish_heights,
+    const StepPlan& L = s->plan;
+    for (int32_t v : {s->N, s->nd, (int)L.generic(), (int)(L.family == FAM_QUAD), (int)L.base, L.stat_cols, L.fused_waves, L.tree_g, L.tree_waves, L.gen_epb, L.gen_lds,
+                      (int)(L.family == FAM_TREE), s->rbs_mode, s->heights_mode, P.self_collisions, P.publish_debug, P.publish_rbs, P.publish_heights,
                       P.stash_pre_reset, P.stat_stride, (int32_t)P.base_active})
         h = fnv_val(h, v);
     h = fnv_val(h, P.bounce_threshold);
@@ -899,7 +968,7 @@ std::vector<StateRegion> state_regions(const grx_sim* s) {
     GRX_REGION(obs, (size_t)s->cfg.num_obs * N + 64); GRX_REGION(pri_obs, (size_t)s->cfg.num_pri_obs * N + 64);
     GRX_REGION(stat_partial, 2 * NSTAT * (size_t)P.stat_stride); GRX_REGION(stat_nblocks, 2);
     GRX_REGION(stat_hist, (size_t)GRX_STATS_HISTORY * NSTAT); GRX_REGION(stats, NSTAT);
-    if (s->base) {
+    if (s->plan.base) {
         GRX_REGION(base_episode_sums, NB * N); GRX_REGION(base_reward_terms, NB * N);
         GRX_REGION(base_stat_partial, (NB + 1) * (size_t)P.stat_stride); GRX_REGION(base_stats, NB); GRX_REGION(base_stat_hist, (size_t)GRX_STATS_HISTORY * NB);
     }
@@ -1001,36 +1070,11 @@ int grx_create(const grx_config* cfg, int device_id, grx_handle* out) {
     s->cfg.terrain_origins = nullptr;
     s->device = device_id;
     s->N = c.num_envs;
-    s->generic = generic; s->nd = nd; s->base = base;
+    s->nd = nd;
     const size_t N = (size_t)c.num_envs;
     KParams& P = s->hp;
     memset(&P, 0, sizeof P);
     P.N = c.num_envs; P.env_offset = c.env_offset; P.total_envs = c.total_envs; P.nd = nd;
-    {   // waves per block: the step kernel needs a SIMD per wave (512 registers/lane).  Four waves per block while the
-        // blocks fit the device's SIMDs in at most TWO rounds (measured on MI355X, rough terrain: 16384 envs = 2 rounds of
-        // the four-wave layout 131 us, two-wave layout 152 us, one-wave layout 170 us; 20480 envs: 192 / 276 / 171 us),
-        // one wave per block beyond; the two-wave layout is never the fastest any more (kept: GRX_WAVES_PER_BLOCK, tests)
-        hipDeviceProp_t prop;
-        HIP_TRY(hipGetDeviceProperties(&prop, device_id));
-        const int simds = prop.multiProcessorCount * 4;
-        const int nblocks = (c.num_envs + grx_envs_per_block() - 1) / grx_envs_per_block();
-        s->waves = nblocks * 4 <= 2 * simds ? 8 : 1;   // (the pipeline with eight waves per block, two per SIMD: +3 % over four at 8192 envs, +1 % at 16384)
-        if (const char* w = getenv("GRX_WAVES_PER_BLOCK")) {
-            const int v = atoi(w);
-            if (v == 1 || v == 2 || v == 4 || v == 8) s->waves = v;
-        }
-        // a lane QUAD per env, 16 envs per block: one block per CU needs all of the CU (four SIMDs' registers, 100+ KB of LDS),
-        // so this layout pays exactly while its blocks fit the device in ONE round -- half the CUs would otherwise idle
-        const int qblocks = (c.num_envs + grx_envs_per_block_quad() - 1) / grx_envs_per_block_quad();
-        s->quad = !generic && s->waves >= 4 && qblocks <= prop.multiProcessorCount && !getenv("GRX_WAVES_PER_BLOCK");
-        if (const char* q = getenv("GRX_LANES_PER_ENV")) s->quad = !generic && atoi(q) == 4;   // tests / A-B runs: 2 or 4
-        if (s->quad) { s->waves = 8; if (const char* w = getenv("GRX_QUAD_WAVES")) s->waves = atoi(w) == 4 ? 4 : 8; }   // eight waves (two per SIMD) unless a test asks for the four-role pipeline
-        // control_type 'V' / 'T' and heading_command (ABI 5; off in every registered task) live in the general one-wave layout only:
-        // the wave pipelines keep the registered tasks' code path
-        if (c.control_type != GRX_CONTROL_P || c.heading_command) { s->quad = false; s->waves = 1; }
-        // so do legged_gym's base reward terms (ABI 7), in entries of their own
-        if (base) { s->quad = false; s->waves = 1; }
-    }
     const char* dbg = getenv("GRX_PUBLISH_DEBUG");   // (tools/: overrides the config either way)
     P.publish_debug = dbg ? atoi(dbg) : c.publish_reward_terms;
     P.seed = c.seed;
@@ -1094,13 +1138,12 @@ int grx_create(const grx_config* cfg, int device_id, grx_handle* out) {
     DA(base_lin_vel, 3 * N); DA(base_ang_vel, 3 * N); DA(proj_grav, 3 * N);
     DA(episode_sums, NT * N); DA(reward_terms, NT * N); DA(heights, (size_t)(nh > 0 ? nh : 1) * N);
     DA(obs, (size_t)c.num_obs * N + 64); DA(pri_obs, (size_t)c.num_pri_obs * N + 64);
-    const int nblocks = (c.num_envs + grx_envs_per_block() - 1) / grx_envs_per_block();
+    const int nblocks = (c.num_envs + GRX_PAIR_EPB - 1) / GRX_PAIR_EPB;
     // a column per block of the writing kernel: 16-env blocks at the least for the fused kernels (lane quads) and the one-lane generic kernel;
     // the tree kernel goes down to one four-env wave per block (16 lanes per env, GRX_TREE_WAVES=1)
     P.stat_stride = (generic ? 8 : 2) * nblocks + 1;
     DA(stat_partial, (size_t)2 * NSTAT * P.stat_stride); DA(stat_nblocks, 2); DA(stat_hist, (size_t)GRX_STATS_HISTORY * NSTAT);
     DA(stats, NSTAT); DA(prof, (size_t)std::max(2 * nblocks, 64) * GRX_PROF_SLOTS);   // (16-env blocks in the quad layout; the tree kernel stamps blocks 0..63 whatever their size)
-    s->base_cols = nblocks;   // (the fused one-wave entry: a wave per 32-env block; the tree / generic kernels: set with their tables below)
     if (base) {
         constexpr int NB = GRX_NUM_BASE_REWARD_TERMS;
         DA(base_episode_sums, NB * N); DA(base_reward_terms, NB * N);
@@ -1390,7 +1433,7 @@ int grx_create(const grx_config* cfg, int device_id, grx_handle* out) {
     desc_vec(s, GRX_T_TERM_CONTACT, P.term_contact, GRX_U8, Ni);
     desc_vec(s, GRX_T_EPISODE_STATS, P.stats, GRX_F32, NSTAT);
     desc_rows(s, GRX_T_EPISODE_STATS_HISTORY, P.stat_hist, GRX_STATS_HISTORY, NSTAT);
-    if (s->base) {   // (ABI 7; a handle without base terms has no such tensors: data stays NULL, grx_tensor refuses them)
+    if (base) {   // (ABI 7; a handle without base terms has no such tensors: data stays NULL, grx_tensor refuses them)
         desc_rows(s, GRX_T_BASE_EPISODE_SUMS, P.base_episode_sums, GRX_NUM_BASE_REWARD_TERMS, Ni);
         desc_rows(s, GRX_T_BASE_REWARD_TERMS, P.base_reward_terms, GRX_NUM_BASE_REWARD_TERMS, Ni);
         desc_vec(s, GRX_T_BASE_EPISODE_STATS, P.base_stats, GRX_F32, GRX_NUM_BASE_REWARD_TERMS);
@@ -1400,28 +1443,12 @@ int grx_create(const grx_config* cfg, int device_id, grx_handle* out) {
     desc_soa3(s, GRX_T_CONTACT_FORCES, P.contact_forces, GRX_MAX_LINKS, 3);
     desc_soa3(s, GRX_T_RIGID_BODY_STATES, P.rbs, GRX_MAX_LINKS, 13);
     if (s->rbs_mode == GRX_PUBLISH_NEVER) s->desc[GRX_T_RIGID_BODY_STATES].data = nullptr;
-    s->prof_host = P.prof; s->prof_blocks = s->quad ? (c.num_envs + grx_envs_per_block_quad() - 1) / grx_envs_per_block_quad() : nblocks;
-    // generic kernel: the per-body workspace goes to LDS when 16 envs' rows fit (155 KB for the 33-body robot: LDS round
-    // trips are ~5x shorter than global ones and the kernel is bound by exactly those); else 64 envs per block over the
-    // global workspace.  GRX_GENERIC_EPB = 16 / 32 / 64 forces a block size over the GLOBAL workspace (A/B runs).
+    rc = plan_layout(s, c, generic, base);
+    if (rc) { grx_destroy(s); return rc; }
+    s->prof_host = P.prof; s->prof_blocks = s->plan.family == FAM_QUAD ? s->plan.grid : nblocks;
     if (generic) {
-        const size_t per_env = (size_t)grx_generic_ws_floats_per_env(m.num_bodies, 24) * sizeof(float);
-        hipDeviceProp_t prop;
-        HIP_TRY(hipGetDeviceProperties(&prop, device_id));
-        // one such block fills a CU's LDS, so this only pays while all blocks run in ONE round (<= 16 envs per CU:
-        // 4096 envs on an MI355X; measured 1.9 ms vs 3.2 ms at 4096 envs, but 7.5 ms vs 3.7 ms at 16384)
-        if (per_env * 16 + 1024 <= 159 * 1024 && (c.num_envs + 15) / 16 <= prop.multiProcessorCount) { s->gen_epb = 16; s->gen_lds = (int)(per_env * 16); }
-        if (const char* ev = getenv("GRX_GENERIC_EPB")) { const int v = atoi(ev); if (v == 16 || v == 32 || v == 64) { s->gen_epb = v; s->gen_lds = 0; } }
-    }
-    if (generic) {
-        rc = build_generic(s, c);
-        if (rc) { grx_destroy(s); return rc; }
-        if (s->d_tree) {
-            const int epw = s->tree_g == GRX_TREE_GMAX ? grx_tree_envs_per_wave16() : grx_tree_envs_per_wave();
-            s->base_cols = (s->N + epw * s->tree_waves - 1) / (epw * s->tree_waves) * s->tree_waves;
-        } else s->base_cols = (s->N + s->gen_epb - 1) / s->gen_epb;
-        if (s->base_cols > s->hp.stat_stride) { grx_destroy(s); return fail(GRX_ERR_UNSUPPORTED_MODEL, "grx_create: more statistics columns than the table holds"); }
-        if (!s->d_tree) {   // the one-lane generic kernel (trees with more than eight chains): no link frames, neither every step nor on refresh (it does not stash the state before a reset)
+        if (s->plan.stat_cols > s->hp.stat_stride) { grx_destroy(s); return fail(GRX_ERR_UNSUPPORTED_MODEL, "grx_create: more statistics columns than the table holds"); }
+        if (s->plan.family == FAM_GENERIC) {   // the one-lane generic kernel (trees with more than eight chains): no link frames, neither every step nor on refresh (it does not stash the state before a reset)
             s->hp.publish_rbs = 0;
             if (s->rbs_mode == GRX_PUBLISH_EVERY_STEP) { s->rbs_mode = GRX_PUBLISH_NEVER; s->desc[GRX_T_RIGID_BODY_STATES].data = nullptr; }
             // (it reads the raw heights back from memory: always materialised there; it neither stashes the state before a reset)
@@ -1520,61 +1547,44 @@ static int capture_needs_flushed_stats(grx_sim* s, const char* who) {
                 "launch are still unreduced, and a recorded kernel cannot reduce them)");
 }
 
-int grx_reset_all(grx_handle s, void* stream) {
-    if (!s) return fail(GRX_ERR_INVALID_ARGUMENT, "grx_reset_all: null handle");
-    hipStream_t st = (hipStream_t)stream;
+// BaseTask.reset()'s reset_idx(all envs) (mask == nullptr) or reset_idx(env_ids) of the envs flagged in mask: one statistics-writing launch
+static int reset_envs(grx_sim* s, uint8_t* mask, const int32_t* env_ids, int32_t n, hipStream_t st, const char* who) {
     // extras["episode"] of a full reset: mean of the running episode sums over all envs
     // (legged_robot.py:420-424); computed by the stats path with every env flagged.
+    const StepPlan& L = s->plan;
     const bool capturing = stream_is_capturing(st);
     if (capturing) s->has_recorded = true;
-    if (capturing) if (int rc = capture_needs_flushed_stats(s, "grx_reset_all")) return rc;
+    if (capturing) if (int rc = capture_needs_flushed_stats(s, who)) return rc;
     ++s->state_epoch;
     uint32_t step = 0x80000000u + (s->reset_count++);
     // (the generic reset kernel does not fold its predecessor's statistics: reduce them now)
-    if (s->generic && !s->stats_current) grx_launch_finalize(s->d_hp, s->eager_seq, nullptr, 0, st);
+    if (L.generic() && !s->stats_current) grx_launch_finalize(s->d_hp, s->eager_seq, nullptr, 0, st);
     const StepSeq q = next_seq(s, st, capturing);
-    if (s->base) grx_launch_base_reset(s->d_hp, s->N, nullptr, st);   // ABI 7: the base terms' sums of the finished episodes (every layout)
-    if (s->generic) {
-        grx_launch_reset_all_generic(s->d_hp, s->d_gen, s->N, s->gen_epb, step, q.seq, nullptr, st);
+    if (mask) grx_launch_mark(env_ids, n, s->N, mask, st);
+    if (L.base) grx_launch_base_reset(s->d_hp, s->N, mask, st);   // ABI 7: the base terms' sums of the finished episodes (every layout; before the reset kernel consumes the flags)
+    if (L.generic()) {
+        grx_launch_reset_all_generic(s->d_hp, s->d_gen, (s->N + L.gen_epb - 1) / L.gen_epb, L.gen_epb, step, q.seq, mask, st);
         grx_launch_finalize(s->d_hp, q.seq, q.progress, q.progress ? s->pace.issued : 0, st);
         if (!capturing) s->stats_current = true;
     } else {
-        grx_launch_reset_all(s->d_hp, s->N, step, &q, nullptr, st);
+        grx_launch_reset_all(s->d_hp, s->N, step, &q, mask, st);
         if (capturing) grx_launch_finalize(s->d_hp, q.seq, nullptr, 0, st);   // recorded into a graph: carries its own reduction, see grx_step
     }
-    if (s->base) grx_launch_base_stats(s->d_hp, q.seq, (s->N + 63) / 64, st);
+    if (L.base) grx_launch_base_stats(s->d_hp, q.seq, (s->N + 63) / 64, st);
     HIP_TRY(hipGetLastError());
     return GRX_OK;
+}
+
+int grx_reset_all(grx_handle s, void* stream) {
+    if (!s) return fail(GRX_ERR_INVALID_ARGUMENT, "grx_reset_all: null handle");
+    return reset_envs(s, nullptr, nullptr, 0, (hipStream_t)stream, "grx_reset_all");
 }
 
 int grx_reset_idx(grx_handle s, const int32_t* env_ids, int32_t n, void* stream) {
     if (!s || (n > 0 && !env_ids)) return fail(GRX_ERR_INVALID_ARGUMENT, "grx_reset_idx: null argument");
     if (n <= 0) return GRX_OK;   // legged_robot.py:387-388
-    hipStream_t st = (hipStream_t)stream;
-    const bool capturing = stream_is_capturing(st);
-    if (capturing) s->has_recorded = true;
-    if (capturing) if (int rc = capture_needs_flushed_stats(s, "grx_reset_idx")) return rc;
-    ++s->state_epoch;
-    uint32_t step = 0x80000000u + (s->reset_count++);
-    if (s->generic && !s->stats_current) grx_launch_finalize(s->d_hp, s->eager_seq, nullptr, 0, st);
-    const StepSeq q = next_seq(s, st, capturing);
-    grx_launch_mark(env_ids, n, s->N, s->d_mask, st);
-    if (s->base) grx_launch_base_reset(s->d_hp, s->N, s->d_mask, st);   // (before the reset kernel consumes the flags; every layout)
-    if (s->generic) {
-        grx_launch_reset_all_generic(s->d_hp, s->d_gen, s->N, s->gen_epb, step, q.seq, s->d_mask, st);
-        grx_launch_finalize(s->d_hp, q.seq, q.progress, q.progress ? s->pace.issued : 0, st);
-        if (!capturing) s->stats_current = true;
-    } else {
-        grx_launch_reset_all(s->d_hp, s->N, step, &q, s->d_mask, st);
-        if (capturing) grx_launch_finalize(s->d_hp, q.seq, nullptr, 0, st);
-    }
-    if (s->base) grx_launch_base_stats(s->d_hp, q.seq, (s->N + 63) / 64, st);
-    HIP_TRY(hipGetLastError());
-    return GRX_OK;
+    return reset_envs(s, s->d_mask, env_ids, n, (hipStream_t)stream, "grx_reset_idx");
 }
-
-// the launchers' `heightfield` argument: 0 plane, 1 the raster as a heightfield, 2 mesh_type 'trimesh' (the *_trimesh kernels: the reference's corrected mesh)
-static int terrain_mode(const grx_sim* s) { return s->cfg.terrain_type == GRX_TERRAIN_HEIGHTFIELD ? (s->cfg.vertical_faces ? 2 : 1) : 0; }
 
 int grx_step(grx_handle s, grx_step_args* a, void* stream) {
     if (!s || !a) return fail(GRX_ERR_INVALID_ARGUMENT, "grx_step: null argument");
@@ -1612,36 +1622,27 @@ int grx_step(grx_handle s, grx_step_args* a, void* stream) {
     a->stats_slot = q.seq & (GRX_STATS_HISTORY - 1);
     a->stats_seq = q.seq;
     s->last_pushed = s->cfg.push_robots && s->cfg.push_interval > 0 && ((uint32_t)a->common_step_counter % (uint32_t)s->cfg.push_interval) == 0;
-    if (s->generic)
-    {
-        if (s->d_tree) {
-            if ((s->tree_g == GRX_TREE_GMAX ? grx_launch_step_tree16 : grx_launch_step_tree)(s->d_hp, s->d_tree, s->d_gen, s->N, s->tree_waves, s->tree_lds, terrain_mode(s), a->actions, a->delay_substeps,
-                                     (long long)a->common_step_counter, a->noise_uniform, a->obs_out, a->pri_obs_out, &q, s->base ? 1 : 0, st))
-                return fail(GRX_ERR_HIP, "grx_step: cannot raise the dynamic LDS limit of the tree kernel");
-        } else if (grx_launch_step_generic(s->d_hp, s->d_gen, s->d_ws, s->N, s->gen_epb, s->gen_lds, terrain_mode(s), a->actions,
-                                    a->delay_substeps, (long long)a->common_step_counter, a->noise_uniform, a->obs_out, a->pri_obs_out, q.seq, s->base ? 1 : 0, st))
-            return fail(GRX_ERR_HIP, "grx_step: cannot raise the dynamic LDS limit of the generic kernel");
-    }
+    const StepPlan& L = s->plan;
+    const long long csc = (long long)a->common_step_counter;
+    if (L.family == FAM_TREE)
+        (L.lanes_per_env == GRX_TREE_GMAX ? grx_launch_step_tree16 : grx_launch_step_tree)(L.row, s->d_hp, s->d_tree, s->d_gen, L.grid, L.waves, L.lds, a->actions, a->delay_substeps, csc,
+                                                                                           a->noise_uniform, a->obs_out, a->pri_obs_out, &q, nullptr, st);
+    else if (L.family == FAM_GENERIC)
+        grx_launch_step_generic(L.row, s->d_hp, s->d_gen, s->d_ws, L.grid, L.block, L.lds, a->actions, a->delay_substeps, csc, a->noise_uniform, a->obs_out, a->pri_obs_out, q.seq, st);
     else
-    {
-        if (s->base) grx_launch_step_base(s->d_hp, s->N, terrain_mode(s), a->actions, a->delay_substeps, (long long)a->common_step_counter, a->noise_uniform,
-                                          a->obs_out, a->pri_obs_out, &q, st);   // ABI 7: legged_gym's base reward terms (one wave per block)
-        else if (s->quad) grx_launch_step_quad(s->d_hp, s->N, terrain_mode(s), s->waves, a->actions, a->delay_substeps,
-                                          (long long)a->common_step_counter, a->noise_uniform, a->obs_out, a->pri_obs_out, &q, st);
-        else grx_launch_step(s->d_hp, s->N, terrain_mode(s), s->waves, a->actions, a->delay_substeps,
-                             (long long)a->common_step_counter, a->noise_uniform, a->obs_out, a->pri_obs_out, &q, st);
-    }
-    if (s->base) {   // the base terms' episode statistics right behind the step, then the command curriculum (one block; returns at once on a step without resets)
-        grx_launch_base_stats(s->d_hp, q.seq, s->base_cols, st);
+        hipLaunchKernelGGL(static_cast<const FusedStepRow*>(L.row)->fn, dim3(L.grid), dim3(L.block), 0, st, s->d_hp, a->actions, a->delay_substeps, csc, a->noise_uniform,
+                           (const float*)nullptr, a->obs_out, a->pri_obs_out, q);
+    if (L.base) {   // the base terms' episode statistics right behind the step, then the command curriculum (one block; returns at once on a step without resets)
+        grx_launch_base_stats(s->d_hp, q.seq, L.stat_cols, st);
         if (s->hp.command_curriculum)
-            grx_launch_curriculum(s->d_hp, s->base_cols, (uint32_t)a->common_step_counter, a->obs_out ? a->obs_out : s->hp.obs, s->cfg.num_obs,
+            grx_launch_curriculum(s->d_hp, L.stat_cols, (uint32_t)a->common_step_counter, a->obs_out ? a->obs_out : s->hp.obs, s->cfg.num_obs,
                                   a->pri_obs_out ? a->pri_obs_out : s->hp.pri_obs, s->cfg.num_pri_obs, st);
     }
     if (timed) {
         HIP_TRY(hipEventRecord(ev.second, st));
         s->timing.pending.push_back(ev);
     }
-    if ((s->generic && !s->d_tree) || capturing) {   // the one-lane generic kernel does not fold its predecessor's statistics: its own small kernel, with the step's ticket
+    if (L.family == FAM_GENERIC || capturing) {   // the one-lane generic kernel does not fold its predecessor's statistics: its own small kernel, with the step's ticket
         grx_launch_finalize(s->d_hp, q.seq, q.progress, q.progress ? s->pace.issued : 0, st);
         if (!capturing) s->stats_current = true;
     }
@@ -1683,7 +1684,7 @@ int grx_tensor(grx_handle s, int id, grx_tensor_desc* out) {
     if (!s || !out) return fail(GRX_ERR_INVALID_ARGUMENT, "grx_tensor: null argument");
     if (id < 0 || id >= GRX_NUM_TENSORS) return fail(GRX_ERR_INVALID_ARGUMENT, "grx_tensor: unknown tensor id");
     if (id == GRX_T_COMMAND_RANGES && !s->hp.command_curriculum) return fail(GRX_ERR_INVALID_ARGUMENT, "grx_tensor: GRX_T_COMMAND_RANGES exists on handles with command_curriculum only");
-    if (id >= GRX_T_BASE_EPISODE_SUMS && !s->base) return fail(GRX_ERR_INVALID_ARGUMENT, "grx_tensor: the base reward term tensors exist on handles with base reward terms only");
+    if (id >= GRX_T_BASE_EPISODE_SUMS && !s->plan.base) return fail(GRX_ERR_INVALID_ARGUMENT, "grx_tensor: the base reward term tensors exist on handles with base reward terms only");
     *out = s->desc[id];
     return GRX_OK;
 }
@@ -1734,33 +1735,9 @@ int grx_stats_seq(grx_handle s, int64_t* out) {
 int grx_layout(grx_handle s, grx_layout_info* out) {
     if (!s || !out) return fail(GRX_ERR_INVALID_ARGUMENT, "grx_layout: null argument");
     memset(out, 0, sizeof *out);
-    const char* hf = s->cfg.terrain_type == GRX_TERRAIN_HEIGHTFIELD ? "true" : "false";
-    const bool tm = terrain_mode(s) == 2;   // mesh_type 'trimesh': the *_trimesh entries of the same kernels
-    if (s->generic && s->d_tree) {
-        out->lanes_per_env = s->tree_g; out->waves_per_block = s->tree_waves; out->envs_per_block = (s->tree_g == GRX_TREE_GMAX ? grx_tree_envs_per_wave16() : grx_tree_envs_per_wave()) * s->tree_waves;
-        const char* t = s->tree_g == GRX_TREE_GMAX ? "grx_step_tree16" : "grx_step_tree";
-        const char* b = s->base ? "_base" : "";   // (ABI 7: the entries with legged_gym's base reward terms)
-        if (tm) snprintf(out->kernel, sizeof out->kernel, "%s%s_trimesh<false>", t, b);
-        else snprintf(out->kernel, sizeof out->kernel, "%s%s<%s, false>", t, b, hf);
-    } else if (s->generic) {
-        out->lanes_per_env = 1; out->waves_per_block = 1; out->envs_per_block = s->gen_epb;
-        const char* b = s->base ? "_base" : "";
-        if (tm) snprintf(out->kernel, sizeof out->kernel, "grx_step_generic%s_trimesh", b);
-        else snprintf(out->kernel, sizeof out->kernel, "grx_step_generic%s<%s>", b, hf);
-    } else if (s->base) {
-        out->lanes_per_env = 2; out->waves_per_block = 1; out->envs_per_block = grx_envs_per_block();
-        if (tm) snprintf(out->kernel, sizeof out->kernel, "grx_step_kernel_base_trimesh<false>");
-        else snprintf(out->kernel, sizeof out->kernel, "grx_step_kernel_base<%s, false>", hf);
-    } else if (s->quad) {
-        out->lanes_per_env = 4; out->waves_per_block = s->waves; out->envs_per_block = grx_envs_per_block_quad();
-        if (tm) snprintf(out->kernel, sizeof out->kernel, "grx_step_kernel_quad_trimesh<%d, false>", s->waves);
-        else snprintf(out->kernel, sizeof out->kernel, "grx_step_kernel_quad<%s, %d, false>", hf, s->waves);
-    } else {
-        out->lanes_per_env = 2; out->waves_per_block = s->waves; out->envs_per_block = grx_envs_per_block();
-        if (tm) snprintf(out->kernel, sizeof out->kernel, "grx_step_kernel_trimesh<%d, false>", s->waves);
-        else snprintf(out->kernel, sizeof out->kernel, "grx_step_kernel<%s, %d, false>", hf, s->waves);
-    }
-    out->num_blocks = (s->N + out->envs_per_block - 1) / out->envs_per_block;
+    const StepPlan& L = s->plan;
+    out->lanes_per_env = L.lanes_per_env; out->waves_per_block = L.waves; out->envs_per_block = L.envs_per_block; out->num_blocks = L.grid;
+    snprintf(out->kernel, sizeof out->kernel, "%s", L.row->name);   // the table row's name IS the kernel grx_step launches
     return GRX_OK;
 }
 
@@ -1798,7 +1775,8 @@ int grx_debug_profile(grx_handle s, long long* out, int max_blocks) {
 // buffers + the debug rows, then launches the DBG instantiation (no sub-steps) of the step kernel this handle runs.
 int grx_debug_post_physics(grx_handle s, const grx_pipeline_state* ps, int apply_reset, const grx_step_args* a, void* stream) {
     if (!s || !ps || !a) return fail(GRX_ERR_INVALID_ARGUMENT, "grx_debug_post_physics: null argument");
-    if (s->generic && !s->d_tree) return fail(GRX_ERR_UNSUPPORTED_MODEL, "grx_debug_post_physics: the fused kernels or the tree kernel only (this model runs on the one-lane generic kernel)");
+    const StepPlan& L = s->plan;
+    if (L.family == FAM_GENERIC) return fail(GRX_ERR_UNSUPPORTED_MODEL, "grx_debug_post_physics: the fused kernels or the tree kernel only (this model runs on the one-lane generic kernel)");
     hipStream_t st = (hipStream_t)stream;
     const size_t N = (size_t)s->N;
     const int nd = s->nd, rows = grx_debug_rows(), r_tor = grx_debug_row_of(0), r_lla = grx_debug_row_of(1), r_term = grx_debug_row_of(2), r_apply = grx_debug_row_of(3);
@@ -1838,17 +1816,14 @@ int grx_debug_post_physics(grx_handle s, const grx_pipeline_state* ps, int apply
 #undef UPS
     HIP_TRY(hipStreamSynchronize(st));   // the host vectors go out of scope
     const StepSeq sq = next_seq(s, st, false);
-    // the post-physics half of the kernel this handle steps with (lane pairs: 1 / 4 / 8 waves; lane quads: 4 / 8; GRX_FORCE_GENERIC: the tree kernel)
-    if (s->generic) {
-        if ((s->tree_g == GRX_TREE_GMAX ? grx_launch_step_tree_debug16 : grx_launch_step_tree_debug)(s->d_hp, s->d_tree, s->d_gen, s->N, s->tree_waves, s->tree_lds, terrain_mode(s), s->d_dbg_actions,
-                                       (long long)a->common_step_counter, a->noise_uniform, s->d_dbg, &sq, s->base ? 1 : 0, st))
-            return fail(GRX_ERR_HIP, "grx_debug_post_physics: cannot raise the dynamic LDS limit of the tree kernel");
-    } else if (s->base) grx_launch_step_debug_base(s->d_hp, s->N, terrain_mode(s), s->d_dbg_actions, (long long)a->common_step_counter, a->noise_uniform, s->d_dbg, &sq, st);
-    else if (s->quad) grx_launch_step_debug_quad(s->d_hp, s->N, terrain_mode(s), s->waves, s->d_dbg_actions,
-                                            (long long)a->common_step_counter, a->noise_uniform, s->d_dbg, &sq, st);
-    else grx_launch_step_debug(s->d_hp, s->N, terrain_mode(s), s->waves, s->d_dbg_actions, (long long)a->common_step_counter,
-                               a->noise_uniform, s->d_dbg, &sq, st);
-    if (s->base) grx_launch_base_stats(s->d_hp, sq.seq, s->base_cols, st);
+    // the post-physics half of the kernel this handle steps with: the DBG row of its key (lane pairs: 1 / 4 / 8 waves; lane quads: 4 / 8; GRX_FORCE_GENERIC: the tree kernel)
+    if (L.family == FAM_TREE)
+        (L.lanes_per_env == GRX_TREE_GMAX ? grx_launch_step_tree16 : grx_launch_step_tree)(L.dbg_row, s->d_hp, s->d_tree, s->d_gen, L.grid, L.waves, L.lds, s->d_dbg_actions, 0.f,
+                                                                                           (long long)a->common_step_counter, a->noise_uniform, nullptr, nullptr, &sq, s->d_dbg, st);
+    else
+        hipLaunchKernelGGL(static_cast<const FusedStepRow*>(L.dbg_row)->fn, dim3(L.grid), dim3(L.dbg_block), 0, st, s->d_hp, s->d_dbg_actions, 0.f, (long long)a->common_step_counter,
+                           a->noise_uniform, s->d_dbg, (float*)nullptr, (float*)nullptr, sq);
+    if (L.base) grx_launch_base_stats(s->d_hp, sq.seq, L.stat_cols, st);
     HIP_TRY(hipGetLastError());
     return GRX_OK;
 }

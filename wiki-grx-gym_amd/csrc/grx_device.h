@@ -253,3 +253,29 @@ struct KParams {
     float *base_stats, *base_stat_hist;                  // [NB], [GRX_STATS_HISTORY][NB]
     int32_t command_curriculum; float max_curriculum;    // legged_robot.py:828-838 (grx_curriculum_kernel widens cmd_lin_vel_x of the DEVICE copy)
 };
+
+// ---- the step kernels' tables: WHERE A NEW TERRAIN HEAD OR LAYOUT IS REGISTERED.  Every translation unit of step kernels keeps one table per
+// kernel family behind the kernels it names (grx_kernels.hip: lane pairs -- compiled a second time by grx_quad.hip: lane quads --, the tree
+// kernel -- a second time by grx_tree16.hip -- and the one-lane generic kernel), ONE ROW PER INSTANTIATION.  grx_create resolves the handle's
+// rows once (plan_layout, grx_capi.cpp); every launch, grx_layout and the snapshot fingerprint read them from there.
+struct StepRow {
+    int terrain;        // key: 0 plane, 1 the raster as a heightfield, 2 mesh_type 'trimesh' (the *_trimesh heads: the reference's corrected mesh)
+    int waves;          // key: waves per block the instantiation is compiled for (0: any -- the tree and generic kernels take them from the launch)
+    int base;           // key: 1 = the *_base entries (ABI 7: legged_gym's base reward terms)
+    int dbg;            // key: 1 = the DBG instantiation (TEST-ONLY, grx_debug_post_physics: no sub-steps, the physics' results injected)
+    const char* name;   // the kernel's demangled symbol name, as tools/kernel_resources.py lists it: what grx_layout reports
+};
+template <class Fn>
+struct StepRowOf : StepRow { Fn fn; };
+template <class Row, int n>
+inline const Row* grx_find_row(const Row (&rows)[n], int terrain, int waves, int base, int dbg) {
+    for (const Row& r : rows) if (r.terrain == terrain && r.waves == waves && r.base == base && r.dbg == dbg) return &r;
+    return nullptr;   // (grx_create refuses the handle)
+}
+// a row out of ONE spelling of the kernel: stringified after macro expansion, so grx_quad.hip's and grx_tree16.hip's renamed kernels report their own names
+#define GRX_STR_(...) #__VA_ARGS__
+#define GRX_STR(...) GRX_STR_(__VA_ARGS__)
+#define GRX_STEP_ROW(terrain, waves, base, dbg, ...) {{terrain, waves, base, dbg, GRX_STR(__VA_ARGS__)}, __VA_ARGS__}
+// the lane-pair / lane-quad kernels' arguments hold no type private to their translation unit: grx_capi.cpp launches them itself
+typedef StepRowOf<void (*)(const KParams*, const float*, float, long long, const float*, const float*, float*, float*, const StepSeq)> FusedStepRow;   // (= GRX_STEP_KERNEL_ARGS)
+constexpr int GRX_PAIR_EPB = 32;   // envs per block of the lane-pair kernels (a wave64 of lane pairs): the unit the statistics tables are sized in

@@ -73,6 +73,7 @@ constexpr int NSTAT = GRX_NSTAT;
 constexpr bool kBaseTerms = false;   // the step kernel body: legged_gym's base reward terms (shadowed by the grx_step_kernel_base* heads)
 constexpr int LEG = GRX_LEG;
 constexpr int EPB = 64 / LPE;  // envs per block: one wave64 = 32 lane pairs (16 lane quads in grx_quad.hip)
+static_assert(LPE != 2 || EPB == GRX_PAIR_EPB, "grx_device.h sizes the statistics tables in lane-pair blocks");
 
 // ---- episode statistics (extras["episode"], legged_robot.py:387-388, 420-428) without a kernel of their own -----------------
 // Every kernel that finishes episodes (step, reset, debug step) leaves per-block partial sums in the table of its launch parity
@@ -1722,10 +1723,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GRX_WPE, GRX
 #include "grx_step_kernel_body.inc"
 }
 
-// -DGRX_SPIN_LIMIT builds (grx_flags.h): where an expired spin reports before it traps -- one pointer per translation unit
-#if defined(GRX_TREE16_TU)
-extern "C" int grx_set_spin_word_tree16(unsigned long long* p) {
-#elif defined(GRX_QUAD_TU)
+// -DGRX_SPIN_LIMIT builds (grx_flags.h): where an expired spin reports before it traps -- one pointer per translation unit whose kernels spin
+// (grx_tree16.hip: the tree kernels do not)
+#ifndef GRX_TREE16_TU
+#ifdef GRX_QUAD_TU
 extern "C" int grx_set_spin_word_quad(unsigned long long* p) {
 #else
 extern "C" int grx_set_spin_word(unsigned long long* p) {
@@ -1737,36 +1738,63 @@ extern "C" int grx_set_spin_word(unsigned long long* p) {
     return 0;   // (product build: spins are unbounded)
 #endif
 }
+#endif
 
+// The lane-pair kernels' table (grx_device.h, "the step kernels' tables"); compiled by grx_quad.hip with GRX_LPE = 4, the lane-QUAD kernels' -- a
+// lane quad per env, 16 envs per block, W = 4 (the roles of grx_wavepipe.h's header) or 8 (two waves per SIMD: four more roles take work off
+// wave 0's chain): at <= 16 envs per CU (4096 envs on an MI355X) every CU gets a block instead of every other one.
+// Columns: terrain, waves, base, dbg, kernel.  New rows go to the end of a table: the rows' order is the order the kernels are instantiated in,
+// hence their order in the code object, and the bounded-spin build's kernels address a global PC-relatively -- a kernel that moves is, byte
+// for byte, another kernel to `tools/kernel_resources.py --compare`.
+#ifndef GRX_TREE16_TU
 #ifdef GRX_QUAD_TU
-// grx_quad.hip: this translation unit built with GRX_LPE = 4 -- the four-wave step kernel with a lane QUAD per env, 16 envs per
-// block: at <= 16 envs per CU (4096 envs on an MI355X) every CU gets a block instead of every other one
-// waves: 4 (the roles of grx_wavepipe.h's header) or 8 (two waves per SIMD: four more roles take work off wave 0's chain)
-extern "C" void grx_launch_step_quad(const KParams* dP, int N, int heightfield, int waves, const float* actions, float delay, long long common_step,
-                                     const float* noise, float* obs_out, float* pri_out, const StepSeq* sq, hipStream_t stream) {
-    const int nblocks = (N + EPB - 1) / EPB;
-#define GRX_LAUNCH_QUAD(HF_, W_) hipLaunchKernelGGL((grx_step_kernel<HF_, W_>), dim3(nblocks), dim3(64 * W_), 0, stream, dP, actions, delay, common_step, noise, (const float*)nullptr, obs_out, pri_out, *sq)
-#define GRX_LAUNCH_QUAD_TM(W_) hipLaunchKernelGGL((grx_step_kernel_trimesh<W_>), dim3(nblocks), dim3(64 * W_), 0, stream, dP, actions, delay, common_step, noise, (const float*)nullptr, obs_out, pri_out, *sq)
-    if (heightfield == 1) { if (waves == 8) GRX_LAUNCH_QUAD(true, 8); else GRX_LAUNCH_QUAD(true, 4); }   // (heightfield: 0 plane, 1 raster, 2 trimesh)
-    else if (heightfield == 0) { if (waves == 8) GRX_LAUNCH_QUAD(false, 8); else GRX_LAUNCH_QUAD(false, 4); }
-    else { if (waves == 8) GRX_LAUNCH_QUAD_TM(8); else GRX_LAUNCH_QUAD_TM(4); }
-#undef GRX_LAUNCH_QUAD
-#undef GRX_LAUNCH_QUAD_TM
-}
-extern "C" int grx_envs_per_block_quad(void) { return EPB; }
-// TEST-ONLY (grx_debug_post_physics): the post-physics half of the lane-quad kernels on injected state
-extern "C" void grx_launch_step_debug_quad(const KParams* dP, int N, int heightfield, int waves, const float* actions, long long common_step, const float* noise,
-                                           const float* dbg, const StepSeq* sq, hipStream_t stream) {
-    const int nblocks = (N + EPB - 1) / EPB;
-#define GRX_LAUNCH_DBGQ(HF_, W_) hipLaunchKernelGGL((grx_step_kernel<HF_, W_, true>), dim3(nblocks), dim3(64 * W_), 0, stream, dP, actions, 0.f, common_step, noise, dbg, (float*)nullptr, (float*)nullptr, *sq)
-#define GRX_LAUNCH_DBGQ_TM(W_) hipLaunchKernelGGL((grx_step_kernel_trimesh<W_, true>), dim3(nblocks), dim3(64 * W_), 0, stream, dP, actions, 0.f, common_step, noise, dbg, (float*)nullptr, (float*)nullptr, *sq)
-    if (heightfield == 1) { if (waves == 8) GRX_LAUNCH_DBGQ(true, 8); else GRX_LAUNCH_DBGQ(true, 4); }
-    else if (heightfield == 0) { if (waves == 8) GRX_LAUNCH_DBGQ(false, 8); else GRX_LAUNCH_DBGQ(false, 4); }
-    else { if (waves == 8) GRX_LAUNCH_DBGQ_TM(8); else GRX_LAUNCH_DBGQ_TM(4); }
-#undef GRX_LAUNCH_DBGQ
-#undef GRX_LAUNCH_DBGQ_TM
-}
+#define GRX_PAIR_ROW(...)
 #else
+#define GRX_PAIR_ROW(...) GRX_STEP_ROW(__VA_ARGS__),   // lane pairs only: the one- and two-wave layouts, the base reward terms' entries
+#endif
+static const FusedStepRow kFusedRows[] = {
+    GRX_STEP_ROW(1, 8, 0, 0, grx_step_kernel<true, 8, false>),
+    GRX_STEP_ROW(1, 4, 0, 0, grx_step_kernel<true, 4, false>),
+    GRX_PAIR_ROW(1, 2, 0, 0, grx_step_kernel<true, 2, false>)
+    GRX_PAIR_ROW(1, 1, 0, 0, grx_step_kernel<true, 1, false>)
+    GRX_STEP_ROW(0, 8, 0, 0, grx_step_kernel<false, 8, false>),
+    GRX_STEP_ROW(0, 4, 0, 0, grx_step_kernel<false, 4, false>),
+    GRX_PAIR_ROW(0, 2, 0, 0, grx_step_kernel<false, 2, false>)
+    GRX_PAIR_ROW(0, 1, 0, 0, grx_step_kernel<false, 1, false>)
+    GRX_STEP_ROW(2, 8, 0, 0, grx_step_kernel_trimesh<8, false>),
+    GRX_STEP_ROW(2, 4, 0, 0, grx_step_kernel_trimesh<4, false>),
+    GRX_PAIR_ROW(2, 2, 0, 0, grx_step_kernel_trimesh<2, false>)
+    GRX_PAIR_ROW(2, 1, 0, 0, grx_step_kernel_trimesh<1, false>)
+    GRX_STEP_ROW(1, 8, 0, 1, grx_step_kernel<true, 8, true>),
+    GRX_STEP_ROW(1, 4, 0, 1, grx_step_kernel<true, 4, true>),
+    GRX_PAIR_ROW(1, 1, 0, 1, grx_step_kernel<true, 1, true>)
+    GRX_STEP_ROW(0, 8, 0, 1, grx_step_kernel<false, 8, true>),
+    GRX_STEP_ROW(0, 4, 0, 1, grx_step_kernel<false, 4, true>),
+    GRX_PAIR_ROW(0, 1, 0, 1, grx_step_kernel<false, 1, true>)
+    GRX_STEP_ROW(2, 8, 0, 1, grx_step_kernel_trimesh<8, true>),
+    GRX_STEP_ROW(2, 4, 0, 1, grx_step_kernel_trimesh<4, true>),
+    GRX_PAIR_ROW(2, 1, 0, 1, grx_step_kernel_trimesh<1, true>)
+    GRX_PAIR_ROW(1, 1, 1, 0, grx_step_kernel_base<true, false>)
+    GRX_PAIR_ROW(0, 1, 1, 0, grx_step_kernel_base<false, false>)
+    GRX_PAIR_ROW(2, 1, 1, 0, grx_step_kernel_base_trimesh<false>)
+    GRX_PAIR_ROW(1, 1, 1, 1, grx_step_kernel_base<true, true>)
+    GRX_PAIR_ROW(0, 1, 1, 1, grx_step_kernel_base<false, true>)
+    GRX_PAIR_ROW(2, 1, 1, 1, grx_step_kernel_base_trimesh<true>)
+};
+#undef GRX_PAIR_ROW
+// the row of a key (nullptr: none) and the envs of a block, whatever its waves.  dbg: the post-physics half of the step on injected state, in
+// the layout the handle steps with (waves = 1, 4, 8; the two-wave layout shares the one-wave kernel's post-physics code and is served by it)
+#ifdef GRX_QUAD_TU
+extern "C" const FusedStepRow* grx_step_row_quad(int terrain, int waves, int base, int dbg, int* envs_per_block) {
+#else
+extern "C" const FusedStepRow* grx_step_row(int terrain, int waves, int base, int dbg, int* envs_per_block) {
+#endif
+    *envs_per_block = EPB;
+    return grx_find_row(kFusedRows, terrain, dbg && waves == 2 ? 1 : waves, base, dbg);
+}
+#endif
+
+#ifndef GRX_QUAD_TU
 #ifndef GRX_TREE16_TU   // (grx_tree16.hip: only the tree kernel's launchers below)
 // extras["episode"] (legged_robot.py:420-428) ON DEMAND: the reduction stats_fold_previous would do in the handle's next launch,
 // for the launch `seq`, now (grx_flush_stats / grx_episode_stats; the generic-tree kernel's step still ends with it).  The next
@@ -2026,81 +2054,32 @@ extern "C" void grx_launch_refresh_rbs(const KParams* dP, int N, int nlinks, int
     if (n) hipLaunchKernelGGL(grx_refresh_rbs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, dP, pushed);
 }
 
-// host-callable launchers (grx_capi.cpp is compiled by hipcc too; kept separate for readability)
-// waves: waves per 32-env block (1, 2 or 4; grx_capi.cpp picks the largest that still gives every wave its own SIMD)
-extern "C" void grx_launch_step(const KParams* dP, int N, int heightfield, int waves, const float* actions, float delay, long long common_step,
-                                const float* noise, float* obs_out, float* pri_out, const StepSeq* sq, hipStream_t stream) {
-    int nblocks = (N + EPB - 1) / EPB;
-#define GRX_LAUNCH_STEP(HF_, W_) hipLaunchKernelGGL((grx_step_kernel<HF_, W_>), dim3(nblocks), dim3(64 * W_), 0, stream, dP, actions, delay, common_step, noise, (const float*)nullptr, obs_out, pri_out, *sq)
-#define GRX_LAUNCH_STEP_TM(W_) hipLaunchKernelGGL((grx_step_kernel_trimesh<W_>), dim3(nblocks), dim3(64 * W_), 0, stream, dP, actions, delay, common_step, noise, (const float*)nullptr, obs_out, pri_out, *sq)
-    if (heightfield == 1) { if (waves == 8) GRX_LAUNCH_STEP(true, 8); else if (waves == 4) GRX_LAUNCH_STEP(true, 4); else if (waves == 2) GRX_LAUNCH_STEP(true, 2); else GRX_LAUNCH_STEP(true, 1); }   // (heightfield: 0 plane, 1 raster, 2 trimesh)
-    else if (heightfield == 0) { if (waves == 8) GRX_LAUNCH_STEP(false, 8); else if (waves == 4) GRX_LAUNCH_STEP(false, 4); else if (waves == 2) GRX_LAUNCH_STEP(false, 2); else GRX_LAUNCH_STEP(false, 1); }
-    else { if (waves == 8) GRX_LAUNCH_STEP_TM(8); else if (waves == 4) GRX_LAUNCH_STEP_TM(4); else if (waves == 2) GRX_LAUNCH_STEP_TM(2); else GRX_LAUNCH_STEP_TM(1); }
-#undef GRX_LAUNCH_STEP
-#undef GRX_LAUNCH_STEP_TM
-}
-// TEST-ONLY (grx_debug_post_physics): the post-physics half of the step on injected state, in the layout the handle steps with
-// (waves = 1, 4, 8; the two-wave layout shares the one-wave kernel's post-physics code and is served by it)
-extern "C" void grx_launch_step_debug(const KParams* dP, int N, int heightfield, int waves, const float* actions, long long common_step, const float* noise,
-                                      const float* dbg, const StepSeq* sq, hipStream_t stream) {
-    int nblocks = (N + EPB - 1) / EPB;
-#define GRX_LAUNCH_DBG(HF_, W_) hipLaunchKernelGGL((grx_step_kernel<HF_, W_, true>), dim3(nblocks), dim3(64 * W_), 0, stream, dP, actions, 0.f, common_step, noise, dbg, (float*)nullptr, (float*)nullptr, *sq)
-#define GRX_LAUNCH_DBG_TM(W_) hipLaunchKernelGGL((grx_step_kernel_trimesh<W_, true>), dim3(nblocks), dim3(64 * W_), 0, stream, dP, actions, 0.f, common_step, noise, dbg, (float*)nullptr, (float*)nullptr, *sq)
-    if (heightfield == 1) { if (waves == 8) GRX_LAUNCH_DBG(true, 8); else if (waves == 4) GRX_LAUNCH_DBG(true, 4); else GRX_LAUNCH_DBG(true, 1); }
-    else if (heightfield == 0) { if (waves == 8) GRX_LAUNCH_DBG(false, 8); else if (waves == 4) GRX_LAUNCH_DBG(false, 4); else GRX_LAUNCH_DBG(false, 1); }
-    else { if (waves == 8) GRX_LAUNCH_DBG_TM(8); else if (waves == 4) GRX_LAUNCH_DBG_TM(4); else GRX_LAUNCH_DBG_TM(1); }
-#undef GRX_LAUNCH_DBG
-#undef GRX_LAUNCH_DBG_TM
-}
-// ABI 7: the one-wave entries with legged_gym's base reward terms (heightfield: 0 plane, 1 raster, 2 trimesh)
-extern "C" void grx_launch_step_base(const KParams* dP, int N, int heightfield, const float* actions, float delay, long long common_step,
-                                     const float* noise, float* obs_out, float* pri_out, const StepSeq* sq, hipStream_t stream) {
-    const int nblocks = (N + EPB - 1) / EPB;
-    if (heightfield == 1) hipLaunchKernelGGL((grx_step_kernel_base<true>), dim3(nblocks), dim3(64), 0, stream, dP, actions, delay, common_step, noise, (const float*)nullptr, obs_out, pri_out, *sq);
-    else if (heightfield == 0) hipLaunchKernelGGL((grx_step_kernel_base<false>), dim3(nblocks), dim3(64), 0, stream, dP, actions, delay, common_step, noise, (const float*)nullptr, obs_out, pri_out, *sq);
-    else hipLaunchKernelGGL((grx_step_kernel_base_trimesh<>), dim3(nblocks), dim3(64), 0, stream, dP, actions, delay, common_step, noise, (const float*)nullptr, obs_out, pri_out, *sq);
-}
-extern "C" void grx_launch_step_debug_base(const KParams* dP, int N, int heightfield, const float* actions, long long common_step, const float* noise,
-                                           const float* dbg, const StepSeq* sq, hipStream_t stream) {
-    const int nblocks = (N + EPB - 1) / EPB;
-    if (heightfield == 1) hipLaunchKernelGGL((grx_step_kernel_base<true, true>), dim3(nblocks), dim3(64), 0, stream, dP, actions, 0.f, common_step, noise, dbg, (float*)nullptr, (float*)nullptr, *sq);
-    else if (heightfield == 0) hipLaunchKernelGGL((grx_step_kernel_base<false, true>), dim3(nblocks), dim3(64), 0, stream, dP, actions, 0.f, common_step, noise, dbg, (float*)nullptr, (float*)nullptr, *sq);
-    else hipLaunchKernelGGL((grx_step_kernel_base_trimesh<true>), dim3(nblocks), dim3(64), 0, stream, dP, actions, 0.f, common_step, noise, dbg, (float*)nullptr, (float*)nullptr, *sq);
-}
 extern "C" int grx_debug_rows(void) { return DBG_ROWS; }
 extern "C" int grx_debug_row_of(int what) { return what == 0 ? (int)DBG_TORQUES : what == 1 ? (int)DBG_LAST_LAST_ACTIONS : what == 2 ? (int)DBG_TERM_CONTACT : (int)DBG_APPLY_RESET; }
-// epb: envs per block (= threads per block, at most 64); lds_bytes > 0: the per-body workspace lives in (dynamic) LDS
-extern "C" int grx_launch_step_generic(const KParams* dP, const void* tables, float* ws, int N, int epb, int lds_bytes, int heightfield,
-                                       const float* actions, float delay, long long common_step, const float* noise, float* obs_out, float* pri_out,
-                                       long long seq, int base, hipStream_t stream) {   // base: the grx_step_generic_base* entries (ABI 7)
-    const int nblocks = (N + epb - 1) / epb;
-    const GenTables* T = static_cast<const GenTables*>(tables);
-    if (lds_bytes > 0) {
-        static bool raised = false;
-        if (!raised) {   // > 64 KB of dynamic LDS needs the opt-in
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_generic<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_generic<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_generic_trimesh), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_generic_base<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_generic_base<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_generic_base_trimesh), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
-            raised = true;
-        }
-        ws = nullptr;
-    }
-    if (base) {
-        if (heightfield == 2) hipLaunchKernelGGL(grx_step_generic_base_trimesh, dim3(nblocks), dim3(epb), lds_bytes, stream, dP, T, ws, actions, delay, common_step, noise, obs_out, pri_out, seq);
-        else if (heightfield) hipLaunchKernelGGL(grx_step_generic_base<true>, dim3(nblocks), dim3(epb), lds_bytes, stream, dP, T, ws, actions, delay, common_step, noise, obs_out, pri_out, seq);
-        else hipLaunchKernelGGL(grx_step_generic_base<false>, dim3(nblocks), dim3(epb), lds_bytes, stream, dP, T, ws, actions, delay, common_step, noise, obs_out, pri_out, seq);
-        return 0;
-    }
-    if (heightfield == 2) hipLaunchKernelGGL(grx_step_generic_trimesh, dim3(nblocks), dim3(epb), lds_bytes, stream, dP, T, ws, actions, delay, common_step, noise, obs_out, pri_out, seq);
-    else if (heightfield) hipLaunchKernelGGL(grx_step_generic<true>, dim3(nblocks), dim3(epb), lds_bytes, stream, dP, T, ws, actions, delay, common_step, noise, obs_out, pri_out, seq);
-    else hipLaunchKernelGGL(grx_step_generic<false>, dim3(nblocks), dim3(epb), lds_bytes, stream, dP, T, ws, actions, delay, common_step, noise, obs_out, pri_out, seq);
-    return 0;
+// The one-lane generic kernels' table: single-wave blocks of the launch's size, no DBG instantiations
+typedef StepRowOf<void (*)(GRX_STEP_GENERIC_ARGS)> GenericStepRow;
+static const GenericStepRow kGenericRows[] = {
+    GRX_STEP_ROW(1, 0, 0, 0, grx_step_generic<true>),
+    GRX_STEP_ROW(0, 0, 0, 0, grx_step_generic<false>),
+    GRX_STEP_ROW(2, 0, 0, 0, grx_step_generic_trimesh),
+    GRX_STEP_ROW(1, 0, 1, 0, grx_step_generic_base<true>),
+    GRX_STEP_ROW(0, 0, 1, 0, grx_step_generic_base<false>),
+    GRX_STEP_ROW(2, 0, 1, 0, grx_step_generic_base_trimesh),
+};
+// the row of a key (nullptr: none); lds_bytes > 0: the per-body workspace lives in (dynamic) LDS -- more than 64 KB of it needs the opt-in (-1: refused)
+extern "C" int grx_generic_row(int terrain, int base, int lds_bytes, const StepRow** row) {
+    const GenericStepRow* r = grx_find_row(kGenericRows, terrain, 0, base, 0);
+    *row = r;
+    return r && lds_bytes > 0 && hipFuncSetAttribute(reinterpret_cast<const void*>(r->fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess ? -1 : 0;
 }
-extern "C" void grx_launch_reset_all_generic(const KParams* dP, const void* tables, int N, int epb, uint32_t step, long long seq, uint8_t* mask, hipStream_t stream) {
-    hipLaunchKernelGGL(grx_reset_all_generic, dim3((N + epb - 1) / epb), dim3(epb), 0, stream, dP, static_cast<const GenTables*>(tables), step, seq, mask);
+// epb: envs per block (= threads per block, at most 64); the workspace ws is unused when it lives in LDS
+extern "C" void grx_launch_step_generic(const StepRow* row, const KParams* dP, const void* tables, float* ws, int nblocks, int epb, int lds_bytes, const float* actions, float delay,
+                                        long long common_step, const float* noise, float* obs_out, float* pri_out, long long seq, hipStream_t stream) {
+    hipLaunchKernelGGL(static_cast<const GenericStepRow*>(row)->fn, dim3(nblocks), dim3(epb), lds_bytes, stream, dP, static_cast<const GenTables*>(tables), lds_bytes > 0 ? nullptr : ws,
+                       actions, delay, common_step, noise, obs_out, pri_out, seq);
+}
+extern "C" void grx_launch_reset_all_generic(const KParams* dP, const void* tables, int nblocks, int epb, uint32_t step, long long seq, uint8_t* mask, hipStream_t stream) {
+    hipLaunchKernelGGL(grx_reset_all_generic, dim3(nblocks), dim3(epb), 0, stream, dP, static_cast<const GenTables*>(tables), step, seq, mask);
 }
 #endif   // !GRX_TREE16_TU
 // the tree kernel (grx_tree.h): 8 lanes per env, two or four 8-env waves per block; grx_tree16.hip: the same with 16 lanes per env (names + "16")
@@ -2109,60 +2088,41 @@ extern "C" void grx_launch_reset_all_generic(const KParams* dP, const void* tabl
 #else
 #define GRX_TREE_FN(n) n
 #endif
-extern "C" int GRX_TREE_FN(grx_tree_lds_bytes)(int nb, int nlc, int nchain, int nsph, int waves) { return (int)sizeof(TreeTab) + waves * 2 * tree_half_words(tree_offsets(nb, nlc, nchain, nsph).total) * 4; }
-extern "C" int GRX_TREE_FN(grx_tree_envs_per_wave)(void) { return TEPW; }
-extern "C" int GRX_TREE_FN(grx_launch_step_tree)(const KParams* dP, const void* tree_tab, const void* gen_tab, int N, int waves, int lds_bytes, int heightfield, const float* actions, float delay,
-                                    long long common_step, const float* noise, float* obs_out, float* pri_out, const StepSeq* sq, int base, hipStream_t stream) {
-    static bool raised = false;
-    if (!raised) {   // > 64 KB of dynamic LDS needs the opt-in
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_tree_base<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_tree_base<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_tree_base_trimesh<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_tree<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_tree<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_tree_trimesh<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
-        raised = true;
-    }
-    const int nblocks = (N + TEPW * waves - 1) / (TEPW * waves);
-    const TreeTab* Tt = static_cast<const TreeTab*>(tree_tab);
-    const GenTables* Tg = static_cast<const GenTables*>(gen_tab);
-    if (base) {   // ABI 7: the grx_step_tree_base* entries
-        if (heightfield == 2) hipLaunchKernelGGL((grx_step_tree_base_trimesh<false>), dim3(nblocks), dim3(64 * waves), lds_bytes, stream, dP, Tt, Tg, actions, delay, common_step, noise, obs_out, pri_out, *sq, (const float*)nullptr);
-        else if (heightfield) hipLaunchKernelGGL((grx_step_tree_base<true, false>), dim3(nblocks), dim3(64 * waves), lds_bytes, stream, dP, Tt, Tg, actions, delay, common_step, noise, obs_out, pri_out, *sq, (const float*)nullptr);
-        else hipLaunchKernelGGL((grx_step_tree_base<false, false>), dim3(nblocks), dim3(64 * waves), lds_bytes, stream, dP, Tt, Tg, actions, delay, common_step, noise, obs_out, pri_out, *sq, (const float*)nullptr);
-        return 0;
-    }
-    if (heightfield == 2) hipLaunchKernelGGL((grx_step_tree_trimesh<false>), dim3(nblocks), dim3(64 * waves), lds_bytes, stream, dP, Tt, Tg, actions, delay, common_step, noise, obs_out, pri_out, *sq, (const float*)nullptr);
-    else if (heightfield) hipLaunchKernelGGL((grx_step_tree<true, false>), dim3(nblocks), dim3(64 * waves), lds_bytes, stream, dP, Tt, Tg, actions, delay, common_step, noise, obs_out, pri_out, *sq, (const float*)nullptr);
-    else hipLaunchKernelGGL((grx_step_tree<false, false>), dim3(nblocks), dim3(64 * waves), lds_bytes, stream, dP, Tt, Tg, actions, delay, common_step, noise, obs_out, pri_out, *sq, (const float*)nullptr);
+// The tree kernels' table (grx_tree16.hip's renames make it that object's own): the waves per block (1, 2 or 4) are the launch's
+typedef StepRowOf<void (*)(GRX_STEP_TREE_ARGS)> TreeStepRow;
+static const TreeStepRow kTreeRows[] = {
+    GRX_STEP_ROW(1, 0, 1, 0, grx_step_tree_base<true, false>),
+    GRX_STEP_ROW(0, 0, 1, 0, grx_step_tree_base<false, false>),
+    GRX_STEP_ROW(2, 0, 1, 0, grx_step_tree_base_trimesh<false>),
+    GRX_STEP_ROW(1, 0, 0, 0, grx_step_tree<true, false>),
+    GRX_STEP_ROW(0, 0, 0, 0, grx_step_tree<false, false>),
+    GRX_STEP_ROW(2, 0, 0, 0, grx_step_tree_trimesh<false>),
+    GRX_STEP_ROW(1, 0, 1, 1, grx_step_tree_base<true, true>),
+    GRX_STEP_ROW(0, 0, 1, 1, grx_step_tree_base<false, true>),
+    GRX_STEP_ROW(2, 0, 1, 1, grx_step_tree_base_trimesh<true>),
+    GRX_STEP_ROW(1, 0, 0, 1, grx_step_tree<true, true>),
+    GRX_STEP_ROW(0, 0, 0, 1, grx_step_tree<false, true>),
+    GRX_STEP_ROW(2, 0, 0, 1, grx_step_tree_trimesh<true>),
+};
+// the product and DBG rows of a key (nullptr: none) and what a block of `waves` waves takes: its envs and its dynamic LDS (the table + a
+// workspace per wave) for a model of nb bodies, nlc shape-carrying links, nchain chains, nsph spheres.  While that LDS fits a CU (more than
+// 64 KB of it needs the opt-in) the limit of the two kernels is raised (-1: refused).
+extern "C" int GRX_TREE_FN(grx_tree_row)(int terrain, int base, int waves, int nb, int nlc, int nchain, int nsph, const StepRow** row, const StepRow** dbg_row, int* envs_per_block, int* lds_bytes) {
+    const TreeStepRow* r[2] = {grx_find_row(kTreeRows, terrain, 0, base, 0), grx_find_row(kTreeRows, terrain, 0, base, 1)};
+    *row = r[0]; *dbg_row = r[1];
+    *envs_per_block = TEPW * waves;
+    *lds_bytes = (int)sizeof(TreeTab) + waves * 2 * tree_half_words(tree_offsets(nb, nlc, nchain, nsph).total) * 4;
+    if (!r[0] || !r[1] || *lds_bytes > 160 * 1024 - 1024) return 0;
+    for (const TreeStepRow* k : r)
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k->fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
     return 0;
 }
-// TEST-ONLY (grx_debug_post_physics): the post-physics half of the tree kernel on injected state (a 10-dof model forced through it)
-extern "C" int GRX_TREE_FN(grx_launch_step_tree_debug)(const KParams* dP, const void* tree_tab, const void* gen_tab, int N, int waves, int lds_bytes, int heightfield, const float* actions,
-                                          long long common_step, const float* noise, const float* dbg, const StepSeq* sq, int base, hipStream_t stream) {
-    static bool raised = false;
-    if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_tree_base<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_tree_base<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_tree_base_trimesh<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_tree<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_tree<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&grx_step_tree_trimesh<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return -1;
-        raised = true;
-    }
-    const int nblocks = (N + TEPW * waves - 1) / (TEPW * waves);
-    const TreeTab* Tt = static_cast<const TreeTab*>(tree_tab);
-    const GenTables* Tg = static_cast<const GenTables*>(gen_tab);
-    if (base) {
-        if (heightfield == 2) hipLaunchKernelGGL((grx_step_tree_base_trimesh<true>), dim3(nblocks), dim3(64 * waves), lds_bytes, stream, dP, Tt, Tg, actions, 0.f, common_step, noise, (float*)nullptr, (float*)nullptr, *sq, dbg);
-        else if (heightfield) hipLaunchKernelGGL((grx_step_tree_base<true, true>), dim3(nblocks), dim3(64 * waves), lds_bytes, stream, dP, Tt, Tg, actions, 0.f, common_step, noise, (float*)nullptr, (float*)nullptr, *sq, dbg);
-        else hipLaunchKernelGGL((grx_step_tree_base<false, true>), dim3(nblocks), dim3(64 * waves), lds_bytes, stream, dP, Tt, Tg, actions, 0.f, common_step, noise, (float*)nullptr, (float*)nullptr, *sq, dbg);
-        return 0;
-    }
-    if (heightfield == 2) hipLaunchKernelGGL((grx_step_tree_trimesh<true>), dim3(nblocks), dim3(64 * waves), lds_bytes, stream, dP, Tt, Tg, actions, 0.f, common_step, noise, (float*)nullptr, (float*)nullptr, *sq, dbg);
-    else if (heightfield) hipLaunchKernelGGL((grx_step_tree<true, true>), dim3(nblocks), dim3(64 * waves), lds_bytes, stream, dP, Tt, Tg, actions, 0.f, common_step, noise, (float*)nullptr, (float*)nullptr, *sq, dbg);
-    else hipLaunchKernelGGL((grx_step_tree<false, true>), dim3(nblocks), dim3(64 * waves), lds_bytes, stream, dP, Tt, Tg, actions, 0.f, common_step, noise, (float*)nullptr, (float*)nullptr, *sq, dbg);
-    return 0;
+// row: the product kernel's, or (TEST-ONLY, grx_debug_post_physics) the DBG one's with the injected rows in dbg: the post-physics half of the
+// tree kernel on injected state (a 10-dof model forced through it)
+extern "C" void GRX_TREE_FN(grx_launch_step_tree)(const StepRow* row, const KParams* dP, const void* tree_tab, const void* gen_tab, int nblocks, int waves, int lds_bytes, const float* actions,
+                                                  float delay, long long common_step, const float* noise, float* obs_out, float* pri_out, const StepSeq* sq, const float* dbg, hipStream_t stream) {
+    hipLaunchKernelGGL(static_cast<const TreeStepRow*>(row)->fn, dim3(nblocks), dim3(64 * waves), lds_bytes, stream, dP, static_cast<const TreeTab*>(tree_tab), static_cast<const GenTables*>(gen_tab),
+                       actions, delay, common_step, noise, obs_out, pri_out, *sq, dbg);
 }
 #ifndef GRX_TREE16_TU
 extern "C" int grx_generic_tables_size(void) { return (int)sizeof(GenTables); }
@@ -2187,7 +2147,6 @@ extern "C" void grx_launch_set_state(const KParams* dP, int N, const float* root
     const int cnt = env_ids ? n : N;
     hipLaunchKernelGGL(grx_set_state_kernel, dim3((cnt + 255) / 256), dim3(256), 0, stream, dP, root, q, qd, env_ids, n);
 }
-extern "C" int grx_envs_per_block(void) { return EPB; }
 // ABI 7, handles with base reward terms: the finished episodes' base sums of a reset outside a step (grx_reset_all / grx_reset_idx; mask as
 // there, read BEFORE grx_reset_all_kernel consumes it): one env per lane, a column of base_stat_partial per 64-env block, sums zeroed
 __global__ __launch_bounds__(64) void grx_base_reset_kernel(const KParams* __restrict__ Pg, const uint8_t* __restrict__ mask) {
