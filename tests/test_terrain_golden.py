@@ -153,7 +153,7 @@ def _trimesh_tile(name):
 def check_trimesh_surface(query, name, tol):
     """`query((n, 2) points) -> heights` of the build's physics terrain (oracle or HIP) against a vertical ray cast onto the REFERENCE's mesh of the
     same raster (isaacgym terrain_utils.py:286-350 with slope_threshold 0.75, the call of legged_robot.py:903-921).  Round 6: the build holds that
-    mesh itself, a plane per triangle half of every raster cell (oracle trimesh_build / csrc/grx_capi.cpp build_trimesh_tables), so
+    mesh itself, a plane per triangle half of every raster cell (oracle trimesh_build / csrc/grx_host_tables.h build_trimesh_tables), so
       * the two surfaces are the same to `tol` EVERYWHERE a cell's half lies under one triangle of the mesh -- all of the pyramid-stairs tile, whose
         treads are three cells deep and 57 % of whose cells hold a corrected edge or a moved vertex (round 5's band, a quarter-cell ramp then), the
         concave corners' split diagonals included;
@@ -223,7 +223,7 @@ def check_trimesh_walls(ground, wall, name, tol, n_points=4000):
     tests/golden/trimesh_tiles.npz whose projection is a segment.  For spheres of radius 4 cm resting up to 12 cm above the build's ground at random
     places, the true overlap is r - (distance to the closest such triangle whose closest point stands above the ground under the centre).
     The build keeps, per raster cell, the faces on the cell's four sides as rectangles and the ends of faces at its four corners as posts
-    (oracle trimesh_build / csrc/grx_capi.cpp build_trimesh_tables); what that cannot hold -- the notch the corrected mesh leaves along a cell's
+    (oracle trimesh_build / csrc/grx_host_tables.h build_trimesh_tables); what that cannot hold -- the notch the corrected mesh leaves along a cell's
     diagonal at a concave corner, the triangular fins where three levels meet -- is a bounded fraction of the contacts, counted here."""
     cfg, ter, blk, v, t = _trimesh_tile(name)
     a, b, c = v[t[:, 0]], v[t[:, 1]], v[t[:, 2]]
@@ -302,7 +302,7 @@ def test_trimesh_surface_of_every_tile_family():
 
 
 def test_trimesh_tables_of_the_library_equal_the_oracles():
-    """The PRODUCT's host side of mesh_type 'trimesh' on the CPU tier: the per-cell tables grx_create derives from a raster (csrc/grx_capi.cpp
+    """The PRODUCT's host side of mesh_type 'trimesh' on the CPU tier: the per-cell tables grx_create derives from a raster (csrc/grx_host_tables.h
     build_trimesh_tables, reached without a device through the test-only grx_debug_trimesh_tables) are, entry for entry, the ones the oracle builds for
     itself (trimesh_build) -- on the two reference tiles and on the 3 x 10 grid with every tile family.  (What the kernels do with them: the gpu tier.)"""
     import ctypes as C

@@ -110,6 +110,8 @@ struct TreeBody {            // 37 words
 struct TreeDof { float kp, kd, q0, effort, vlim, qlo, qhi, slo, shi, amin, amax, Klim, Clim; int32_t lane; float arm; int32_t pad[2]; };   // 17 words (arm: joint-space armature)
 struct TreeSph { float x, y, z, r, dmax; int32_t slot, link, pad[2]; };   // 9 words
 static_assert(sizeof(TreeBody) == 37 * 4 && sizeof(TreeDof) == 17 * 4 && sizeof(TreeSph) == 9 * 4, "odd strides");
+// compact links that carry collision shapes / self-collision link pairs a generic model may have: they size GenTables (grx_gen_tables.h) and TreeTab
+constexpr int GEN_MAXLC = 24, GEN_MAXLP = 48;
 struct TreeTab {
     int32_t nb, nd, nsph, nlc, nchain, nstep, nh0, g;   // g: lanes per env this table was built for (work list, link / pair rounds)
     int32_t heads0[GRX_TREE_GMAX];                       // lanes whose chain hangs from the base
@@ -118,8 +120,8 @@ struct TreeTab {
     TreeBody body[GRX_MAX_BODIES];
     TreeDof dof[GRX_MAX_DOFS];
     TreeSph sph[GRX_MAX_SPHERES];
-    uint32_t link_flags[24];
-    int32_t link_urdf[24];
+    uint32_t link_flags[GEN_MAXLC];
+    int32_t link_urdf[GEN_MAXLC];
     int32_t foot_body[2], foot_link[2];
     float foot_pos[2][3];
     int32_t torso_body, forehead_body;
@@ -127,14 +129,14 @@ struct TreeTab {
     int32_t sph_begin0, sph_end0;                     // the base's own shapes
     int32_t nlp, pad1;
     // self-collision link pairs (grx_generic.h GenTables.lp_*): bodies, compact links
-    int16_t lp_ba[48], lp_bb[48], lp_a[48], lp_b[48];
+    int16_t lp_ba[GEN_MAXLP], lp_bb[GEN_MAXLP], lp_a[GEN_MAXLP], lp_b[GEN_MAXLP];
     // ... and their sphere pairs (round 6): the broad phase tests EVERY sphere pair of the model (grx_model.pair_a/b) on the sphere centres the
     // contact pass leaves in LDS -- centre distance against (ra + rb + margin)^2 -- and raises the bit of the pair's LINK pair; the narrow phase
     // then runs on the raised link pairs only, i.e. on links that really touch (rounds 2-5 tested the links' bounding spheres, which overlap in
     // every pose for neighbours like upper arm x torso: the 800-instruction narrow phase ran in every round of every sub-step)
     int32_t nsp, nsp_batches;                         // pairs; batches of 4 rounds of the group's lanes (the table is padded with pairs that never pass)
     struct { uint32_t ab; float r2; } sp[GRX_MAX_PAIRS];   // ab: sphere of link a | sphere of link b << 8 | link pair << 16 (positions in sph[]); r2: (ra + rb + margin)^2
-    int32_t lc_begin[25];
+    int32_t lc_begin[GEN_MAXLC + 1];
     int32_t ncs;                                      // rounds of the contact pass
     int32_t nturn;                                    // items of one round that share a body add their forces in turns 0 .. nturn - 1
     int32_t nstep_kin;                                // depth levels that hold a foot, the torso or the forehead: all the final-frames walk needs without GRX_T_RIGID_BODY_STATES

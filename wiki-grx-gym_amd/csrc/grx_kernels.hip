@@ -157,7 +157,7 @@ GRX_DEV void grx_sincos(float x, float& s, float& c) {
 // physics terrain query (oracle: terrain_query): height and gradient (gx, gy) = (dh/dx, dh/dy) of the surface under (x, y).
 //  * heightfield: bilinear patch of the int16 raster (hf_cells: the four corners of a cell in one 8-byte gather);
 //  * mesh_type 'trimesh' (HF == 2: kernels of their own, grx_step_*_trimesh, so that the heightfield's code is what it was): the reference's slope-corrected mesh (isaacgym terrain_utils.py:286-350 moves
-//    vertices by whole cells, so it is still described per raster cell: grx_capi.cpp build_trimesh_tables): the plane of the
+//    vertices by whole cells, so it is still described per raster cell: grx_host_tables.h build_trimesh_tables): the plane of the
 //    triangle half under the point, from that half's three corner heights -- again ONE 8-byte gather; the mesh's vertical
 //    faces are a second contact (wall_contact below).
 // In two halves: the gather (~1.2 us of memory latency on this part) and the interpolation that first USES it -- a caller
@@ -313,7 +313,7 @@ struct SubstepOut {
 
 struct FootKin { V3 pos, vel, ang; };  // foot link origin (world), its velocity, body angular velocity
 
-// Fixed per-lane sphere table layout (grx_capi.cpp build_side_tables): slots 0..7 = this lane's share of the
+// Fixed per-lane sphere table layout (grx_host_tables.h build_side_tables): slots 0..7 = this lane's share of the
 // base-lump shapes, then the chain bodies' shapes.  Unused slots carry r = -1e30 (never within reach).
 __device__ constexpr int kSphCnt[LEG] = {0, 0, 2, 2, 4};
 __device__ constexpr int kSphOff[LEG] = {8, 8, 8, 10, 12};
@@ -1016,7 +1016,7 @@ GRX_DEV FootKin foot_kinematics(const SideConst& C, const LaneState& st) {
 // legged_robot_fftai.py:76): position, orientation (xyzw), linear and angular velocity of every URDF link frame in the state
 // AFTER the last sub-step and BEFORE reset_idx (the reference's tensor is not refreshed by a reset either).  One lane walks
 // its leg once more -- rotations as matrices for the offsets, as quaternions for the orientations -- and stores the frames
-// of the links its tables list (grx_capi.cpp build_rbs_tables).  Only with grx_config.publish_rigid_body_states.
+// of the links its tables list (grx_host_tables.h build_rbs_tables).  Only with grx_config.publish_rigid_body_states.
 GRX_DEV void quat_mul(const float a[4], const float b[4], float o[4]) {   // xyzw
     o[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
     o[1] = a[3] * b[1] - a[0] * b[2] + a[1] * b[3] + a[2] * b[0];
@@ -2125,7 +2125,6 @@ extern "C" void GRX_TREE_FN(grx_launch_step_tree)(const StepRow* row, const KPar
                        actions, delay, common_step, noise, obs_out, pri_out, *sq, dbg);
 }
 #ifndef GRX_TREE16_TU
-extern "C" int grx_generic_tables_size(void) { return (int)sizeof(GenTables); }
 extern "C" int grx_generic_ws_floats_per_env(int nb, int nlc) { return nb * WSB + 3 * nlc; }
 // the statistics of launch `seq` now (grx_flush_stats; the generic path after every step) + optionally a ticket
 extern "C" void grx_launch_finalize(const KParams* dP, long long seq, long long* progress, long long ticket, hipStream_t stream) {
