@@ -48,8 +48,21 @@ def load(precision="f32"):
         lib.gro_debug_wall.argtypes = [H, C.c_double, C.c_double, C.c_double, C.c_double, dp]
         lib.gro_debug_trimesh_tables.argtypes = [H, C.POINTER(C.c_int16), C.POINTER(C.c_int16)]
         lib.gro_debug_import_state.argtypes = [H]
+        lib.gro_debug_rand.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
+        lib.gro_debug_rand.restype = C.c_float
+        lib.gro_debug_stream.argtypes = [C.c_char_p]
         _libs[precision] = (lib, api)
     return _libs[precision]
+
+
+def uniforms(seed, envs, step, stream, items):
+    """The build's own draws gro_rand(seed, global env, step, stream, item) (oracle/philox.h) as a float32 (len(envs), items) array;
+    stream by the name of its GRO_RNG_* id ("RESET_DOF", "PUSH", ...)."""
+    lib, _ = load("f32")
+    sid = lib.gro_debug_stream(stream.encode())
+    if sid < 0:
+        raise KeyError(f"no RNG stream GRO_RNG_{stream}")
+    return np.array([[lib.gro_debug_rand(int(seed), int(e), int(step), sid, i) for i in range(items)] for e in envs], dtype=np.float32).reshape(len(envs), items)
 
 
 class OracleSim(SimHandle):
@@ -128,6 +141,17 @@ class OracleSim(SimHandle):
         if noise_uniform is not None:
             a.noise_uniform = noise_uniform.data_ptr()
         self._check(self.lib.gro_debug_post_physics(self._h, env, C.byref(ps), int(apply_reset), C.byref(a)), "post_physics")
+
+    def debug_post_physics(self, states, apply_reset=False, common_step_counter=1, noise_uniform=None):
+        """post_physics_step of every env on injected records, as ONE step (HipSim.debug_post_physics' signature): with apply_reset the
+        episode statistics of the rows that reset are filed as gro_step files them."""
+        if len(states) != self.num_envs:
+            raise ValueError("debug_post_physics needs one record per env")
+        a = _capi.StepArgs()
+        a.common_step_counter = int(common_step_counter)
+        if noise_uniform is not None:
+            a.noise_uniform = noise_uniform.data_ptr()
+        self._check(self.lib.gro_debug_post_physics(self._h, -1, states, int(bool(apply_reset)), C.byref(a)), "debug_post_physics")
 
     def reward_terms(self, env):
         out = (C.c_float * _capi.NUM_REWARD_TERMS)()

@@ -19,6 +19,7 @@
  *   check_termination           base/legged_robot.py:336-353
  *   compute_reward + 36 terms   base/legged_robot.py:355-375, fftai/...:180-352, gr1t1/gr1t1.py:338-589
  *   reset_idx & friends         base/legged_robot.py:377-440, 650-677, 717-826, fftai/...:137-146
+ *   _get_env_origins            base/legged_robot.py:1163-1195
  *   compute_observations        base/legged_robot.py:442-481, fftai/...:148-167, gr1t1/gr1t1.py:281-336
  *   _get_heights                base/legged_robot.py:1219-1274, utils/math.py:38-42
  *   quaternion helpers          isaacgym/torch_utils.py:43-81,176-190
@@ -26,7 +27,10 @@
  * PARITY STATUS
  *   - env pipeline (everything above except gym.simulate): PINNED against golden vectors produced
  *     by importing the reference Python in the build container (tools/gen_golden.py ->
- *     tests/golden/ (npz fixtures), tests/test_oracle_golden.py).
+ *     tests/golden/ (npz fixtures), tests/test_oracle_golden.py).  The reset family (reset_env,
+ *     update_terrain_curriculum, resample_commands, the push, the origins of gro_create) is pinned by
+ *     reset_family.npz: the reference's live reset_idx fed with this file's own draws
+ *     (tests/test_reset_golden.py, through gro_debug_post_physics).
  *   - physics (gym.simulate, legged_robot_fftai.py:68): **parity unpinned**.  The reference's
  *     physics is the closed NVIDIA Isaac Gym 1.0.preview4 / PhysX 5 binary (absent from the
  *     checkout, .MISSING_LARGE_BLOBS:7-21); there is no source, no golden rollout and no test
@@ -1859,11 +1863,11 @@ typedef struct gro_pipeline_state {
     int32_t term_contact; /* pretend a terminating link carries |F| > threshold */
 } gro_pipeline_state;
 
-/* Runs post_physics_step (everything after the sub-step loop) on injected state; no physics, no reset
- * (reset is reported in RESET but not applied when apply_reset == 0). */
-int gro_debug_post_physics(grx_handle s, int le, const gro_pipeline_state* ps, int apply_reset,
-                           const grx_step_args* args) {
-    if (!s || !ps || le < 0 || le >= s->N) return fail(GRX_ERR_INVALID_ARGUMENT, "gro_debug_post_physics: bad argument");
+/* post_physics_step (everything after the sub-step loop) of env `le` on injected state; no physics.  The same sequence as step_env
+ * after its sub-step loop, the time-based command resample and the push included.  The reset is reported in RESET and applied only
+ * with apply_reset; an applied reset adds the env's episode sums to stats_sum / stats_cnt and clears them, as step_env does. */
+static void debug_post_env(struct grx_sim* s, int le, const gro_pipeline_state* ps, int apply_reset, const grx_step_args* args,
+                           real stats_sum[NT], int* stats_cnt) {
     const grx_config* c = &s->cfg;
     const grx_model* m = &c->model;
     env_t* e = &s->env[le];
@@ -1894,11 +1898,17 @@ int gro_debug_post_physics(grx_handle s, int le, const gro_pipeline_state* ps, i
     quat_rotate_inverse(e->quat, e->vel, e->base_lin_vel);
     quat_rotate_inverse(e->quat, e->ang, e->base_ang_vel);
     quat_rotate_inverse(e->quat, g, e->proj_grav);
-    heading_rule(c, e);   /* (the time-based resample itself is left out here: its draws are not the reference's) */
+    if (c->resample_command_interval > 0 && e->episode_length % c->resample_command_interval == 0)
+        resample_commands(s, e, le, step, GRO_RNG_CMD_TIME);
+    heading_rule(c, e);
     int nh = c->measure_heights ? c->num_height_points : 0;
     if (c->measure_heights) {
         if (c->terrain_type == GRX_TERRAIN_PLANE) for (int k = 0; k < nh; ++k) e->heights[k] = ps->heights[k];
         else measure_heights(s, e);
+    }
+    if (c->push_robots && c->push_interval > 0 && args->common_step_counter % c->push_interval == 0) {
+        e->vel[0] = urand(s, le, step, GRO_RNG_PUSH, 0, -c->max_push_vel_xy, c->max_push_vel_xy);
+        e->vel[1] = urand(s, le, step, GRO_RNG_PUSH, 1, -c->max_push_vel_xy, c->max_push_vel_xy);
     }
     for (int f = 0; f < 2; ++f) {
         e->contact[f] = e->feet_force[f][2] > (real)1.0;
@@ -1929,12 +1939,47 @@ int gro_debug_post_physics(grx_handle s, int le, const gro_pipeline_state* ps, i
         real rew = r[GRX_REW_TERMINATION] * (c->reward_scale[GRX_REW_TERMINATION] * dt);
         e->reward_terms[GRX_REW_TERMINATION] = rew; e->rew += rew; e->episode_sums[GRX_REW_TERMINATION] += rew;
     }
-    if (e->reset && apply_reset) reset_env(s, e, le, step, 1);
+    if (e->reset && apply_reset) {
+        for (int t = 0; t < NT; ++t) { stats_sum[t] += e->episode_sums[t]; e->episode_sums[t] = 0; }
+        *stats_cnt += 1;
+        reset_env(s, e, le, step, 1);
+    }
     build_observations(s, e, le, args, step);
     for (int j = 0; j < nd; ++j) { e->last_actions[j] = e->actions[j]; e->last_dof_vel[j] = e->qd[j]; e->last_last_actions[j] = e->last_actions[j]; }
     for (int f = 0; f < 2; ++f) e->air_time[f] = e->air_time[f] * (e->contact_filt[f] ? 0 : 1);
+}
+
+/* le >= 0: env le alone, from the record *ps; le < 0: every env, from the records ps[0 .. N) (what grx_debug_post_physics takes).
+ * The envs of one call are one step: with apply_reset their episode statistics are filed as gro_step files them. */
+int gro_debug_post_physics(grx_handle s, int le, const gro_pipeline_state* ps, int apply_reset,
+                           const grx_step_args* args) {
+    if (!s || !ps || !args || le >= s->N) return fail(GRX_ERR_INVALID_ARGUMENT, "gro_debug_post_physics: bad argument");
+    real sum[NT];
+    memset(sum, 0, sizeof sum);
+    int cnt = 0;
+    if (le >= 0) debug_post_env(s, le, ps, apply_reset, args, sum, &cnt);
+    else for (int i = 0; i < s->N; ++i) debug_post_env(s, i, ps + i, apply_reset, args, sum, &cnt);
+    if (apply_reset) {
+        if (cnt > 0) {
+            for (int t = 0; t < NT; ++t) s->stats[t] = (float)(sum[t] / cnt / s->cfg.max_episode_length_s);
+            s->stats[NT] = (float)cnt;
+        }
+        stats_file(s, cnt);
+    }
     publish(s);
     return GRX_OK;
+}
+
+/* the build's uniforms as the env code draws them, and the stream ids by name (tools/gen_golden.py gen_reset_family injects them into the
+ * reference; tests/test_reset_golden.py checks the stored ones against today's) */
+float gro_debug_rand(uint64_t seed, uint32_t genv, uint32_t step, uint32_t stream, uint32_t item) { return gro_rand(seed, genv, step, stream, item); }
+int gro_debug_stream(const char* name) {
+    static const struct { const char* n; int id; } k[] = {
+        {"RESET_DOF", GRO_RNG_RESET_DOF}, {"RESET_ROOT", GRO_RNG_RESET_ROOT}, {"CMD_TIME", GRO_RNG_CMD_TIME}, {"CMD_RESET", GRO_RNG_CMD_RESET},
+        {"PUSH", GRO_RNG_PUSH}, {"NOISE", GRO_RNG_NOISE}, {"CURRICULUM", GRO_RNG_CURRICULUM}, {"INIT_DR", GRO_RNG_INIT_DR},
+        {"INIT_LEVEL", GRO_RNG_INIT_LEVEL}, {"NOISE_DOF_L", GRO_RNG_NOISE_DOF_L}, {"NOISE_DOF_R", GRO_RNG_NOISE_DOF_R}};
+    for (size_t i = 0; i < sizeof k / sizeof k[0]; ++i) if (name && !strcmp(name, k[i].n)) return k[i].id;
+    return -1;
 }
 
 /* physics terrain query at world (x, y): out = {height, dh/dx, dh/dy} */

@@ -87,23 +87,17 @@ def test_injected_resets_are_applied_like_the_oracle(layout, monkeypatch):
     c, keep, _ = build_config.build(cfg, cfg.sim.dt, N)
     ora = OracleSim(c, "f32", keep)
     arr = og.states_from(d, "s0_in_", N)
-    for i in range(N):
-        ora.post_physics(i, arr[i], apply_reset=True, common_step_counter=1)
+    ora.debug_post_physics(arr, apply_reset=True, common_step_counter=1)
     sim.debug_post_physics(arr, apply_reset=True, common_step_counter=1)
     torch.cuda.synchronize()
     assert d["s0_out_reset"].sum() >= 3
-    # the oracle's debug entry does not redraw commands on the resampling interval (the kernel does: legged_robot.py:315-317)
-    rows = torch.tensor((d["s0_in_episode_length"] + 1) % int(cfg.commands.resampling_command_interval_s / 0.02) != 0)
+    was_reset = torch.tensor(d["s0_out_reset"].astype(bool))
     for name in ("RESET", "TIME_OUT", "EPISODE_LENGTH", "FEET_CONTACT"):
         assert torch.equal(sim.tensor(name).cpu().to(torch.int64), ora.tensor(name).to(torch.int64)), name
     for name in ("DOF_POS", "DOF_VEL", "ROOT_STATES", "COMMANDS", "OBS", "PRI_OBS", "REW", "LAST_ACTIONS", "FEET_AIR_TIME", "EPISODE_SUMS"):
         a, b = sim.tensor(name).cpu().double(), ora.tensor(name).double()
-        if name == "EPISODE_SUMS":   # (the oracle's debug entry leaves the sums of reset rows in place; its step zeroes them)
-            was_reset = torch.tensor(d["s0_out_reset"].astype(bool))
-            assert float(a[:, was_reset].abs().max()) == 0.0 and float(b[:, was_reset].abs().max()) > 0.0
-            a, b = a[:, rows & ~was_reset], b[:, rows & ~was_reset]
-        else:
-            a, b = a[rows], b[rows]
+        if name == "EPISODE_SUMS":   # the sums of reset rows are filed into the statistics and cleared, on both sides
+            assert float(a[:, was_reset].abs().max()) == 0.0 and float(b[:, was_reset].abs().max()) == 0.0
         assert ((a - b).abs() <= 1e-4 + 1e-4 * b.abs()).all(), name
 
 

@@ -10,6 +10,8 @@ is replaced by a stub: ``gymapi/gymtorch/gymutil`` are MagicMocks, ``torch_utils
 state tensors: quaternion helpers, clip_actions/_compute_torques, the whole
 ``post_physics_step`` (state update, timers, termination, the 24 active reward terms,
 observations incl. injected noise), ``_get_heights``, ``Terrain`` and the rsl_rl PPO pieces.
+Those fixtures stub ``reset_idx`` out; ``gen_reset_family`` runs it live, fed with the build's own
+random draws (which it takes from the oracle library: ``make -C oracle`` first).
 """
 import importlib.util
 import json
@@ -415,33 +417,19 @@ def gen_pipeline(out):
     np.savez(os.path.join(out, "pipeline.npz"), **data)
 
 
-def rough_poses(env, g, tcfg, ter, N):
-    """Poses of gen_pipeline_rough over the reference raster: every scan point at least 5e-4 cells from a cell edge (fp64), base and feet
-    above the local terrain.  Returns the number of redraws."""
+def scan_edge_margin(env, tcfg, i):
+    """Distance (in cells, fp64) of env i's nearest height-scan point to a cell edge of the raster."""
     from legged_gym.utils.math import quat_apply_yaw
+    pts = quat_apply_yaw(env.base_quat[i:i + 1].repeat(1, 121), env.height_points[i:i + 1]).double() + env.root_states[i:i + 1, :3].double().unsqueeze(1)
+    f = (pts[0, :, :2] + tcfg.border_size) / tcfg.horizontal_scale
+    return float((f - torch.round(f)).abs().min())
+
+
+def stand_on_terrain(env, g, tcfg, ter, N):
+    """Heights under the base: put the base and the feet at plausible heights ABOVE the local terrain."""
     hs = torch.tensor(ter.heightsamples.astype(np.int64))
     feet = env.feet_indices
     torso = int(env.torso_indices[0])
-
-    def edge_margin(i):
-        pts = quat_apply_yaw(env.base_quat[i:i + 1].repeat(1, 121), env.height_points[i:i + 1]).double() + env.root_states[i:i + 1, :3].double().unsqueeze(1)
-        f = (pts[0, :, :2] + tcfg.border_size) / tcfg.horizontal_scale
-        return float((f - torch.round(f)).abs().min())
-    redraws = 0
-    for i in range(N):
-        while True:
-            # over the tiles (10 rows x 8 m, 20 columns x 8 m), yaw anywhere, modest tilt; rows 0 / 1 keep randomize_state's poses near
-            # the map corner: the border flat and the first tile
-            if i >= 2:
-                env.root_states[i, 0] = torch.rand((), generator=g) * 78 + 1
-                env.root_states[i, 1] = torch.rand((), generator=g) * 158 + 1
-            env.root_states[i, 3:7] = rand_quat(1, g, tilt=0.4)[0] if i not in (8, 9) else env.root_states[i, 3:7]
-            if edge_margin(i) >= 5e-4:
-                break
-            if i < 2:
-                env.root_states[i, 0:2] += 0.013
-            redraws += 1
-    # heights under the base: put the base and the feet at plausible heights ABOVE the local terrain
     px = ((env.root_states[:, 0] + tcfg.border_size) / tcfg.horizontal_scale).long().clip(0, hs.shape[0] - 2)
     py = ((env.root_states[:, 1] + tcfg.border_size) / tcfg.horizontal_scale).long().clip(0, hs.shape[1] - 2)
     ground = hs[px, py].float() * tcfg.vertical_scale
@@ -451,6 +439,26 @@ def rough_poses(env, g, tcfg, ter, N):
     env.rigid_body_states[:, :, 0:3] = env.root_states[:, None, 0:3]
     env.rigid_body_states[:, feet, 2] = ground[:, None] + torch.rand(N, 2, generator=g) * 0.25
     env.rigid_body_states[:, torso, 3:7] = env.root_states[:, 3:7]
+
+
+def rough_poses(env, g, tcfg, ter, N):
+    """Poses of gen_pipeline_rough over the reference raster: every scan point at least 5e-4 cells from a cell edge (fp64), base and feet
+    above the local terrain.  Returns the number of redraws."""
+    redraws = 0
+    for i in range(N):
+        while True:
+            # over the tiles (10 rows x 8 m, 20 columns x 8 m), yaw anywhere, modest tilt; rows 0 / 1 keep randomize_state's poses near
+            # the map corner: the border flat and the first tile
+            if i >= 2:
+                env.root_states[i, 0] = torch.rand((), generator=g) * 78 + 1
+                env.root_states[i, 1] = torch.rand((), generator=g) * 158 + 1
+            env.root_states[i, 3:7] = rand_quat(1, g, tilt=0.4)[0] if i not in (8, 9) else env.root_states[i, 3:7]
+            if scan_edge_margin(env, tcfg, i) >= 5e-4:
+                break
+            if i < 2:
+                env.root_states[i, 0:2] += 0.013
+            redraws += 1
+    stand_on_terrain(env, g, tcfg, ter, N)
     return redraws
 
 
@@ -497,6 +505,22 @@ def gen_pipeline_rough(out):
     np.savez_compressed(os.path.join(out, "pipeline_rough.npz"), **data)
 
 
+def full_body_link_orientations(env):
+    """The 32-DOF body's torso and forehead orientations in rigid_body_states: the forward kinematics of (root, dof_pos) in fp64 from the
+    model table (tests/kinematics_ref.py), as PhysX would report them."""
+    from wiki_grx_gym_amd.model import RobotModel
+    from tests.kinematics_ref import BodyKinematics
+    rm = RobotModel("gr1t1")
+    kin = BodyKinematics(rm, "cpu")
+    for attr in ("axis", "rot0", "jpos", "link_rot", "link_pos"):
+        setattr(kin, attr, getattr(kin, attr).double())
+    rbs = kin.rigid_body_states(env.root_states.double(), env.dof_pos.double(), env.dof_vel.double())
+    torso = int(env.torso_indices[0])
+    env.rigid_body_states[:, torso, 3:7] = rbs[:, torso, 3:7].float()
+    for fi in env.forehead_indices:
+        env.rigid_body_states[:, int(fi), 3:7] = rbs[:, int(fi), 3:7].float()
+
+
 def gen_pipeline_other_robots(out):
     """One reference post_physics_step() for the robots the round 1-5 fixtures did not cover (VERDICT r5 #4b):
       pipeline_gr1t2.npz      the reference's GR1T2 class with GR1T2LowerLimbCfg and the body names of GR1T2_lower_limb.urdf: its 20-body
@@ -531,17 +555,7 @@ def gen_pipeline_other_robots(out):
             assert imu in term, "GR1T2: 'imu' of terminate_after_contacts_on matches imu_link"
             env.contact_forces[25, imu, 0] = 3.0
         if robot == "gr1t1":
-            from wiki_grx_gym_amd.model import RobotModel
-            from tests.kinematics_ref import BodyKinematics
-            rm = RobotModel("gr1t1")
-            kin = BodyKinematics(rm, "cpu")
-            for attr in ("axis", "rot0", "jpos", "link_rot", "link_pos"):
-                setattr(kin, attr, getattr(kin, attr).double())
-            rbs = kin.rigid_body_states(env.root_states.double(), env.dof_pos.double(), env.dof_vel.double())
-            torso = int(env.torso_indices[0])
-            env.rigid_body_states[:, torso, 3:7] = rbs[:, torso, 3:7].float()
-            for fi in env.forehead_indices:
-                env.rigid_body_states[:, int(fi), 3:7] = rbs[:, int(fi), 3:7].float()
+            full_body_link_orientations(env)
         inp = snapshot_inputs(env)
         env.reset_idx = lambda ids: None
         seen = {}   # every active term on its own (unscaled) AS compute_reward evaluates it inside the step (legged_robot.py:355-375)
@@ -866,6 +880,459 @@ def gen_ppo(out):
              **{"w0_" + k: v.numpy() for k, v in sd0.items()}, **{"w1_" + k: v.detach().numpy() for k, v in sd1.items()})
 
 
+# ---- the reset family: reset_idx, the terrain curriculum, command resampling, pushes, _get_env_origins (tests/golden/reset_family.npz) ----
+class ScriptedDraws:
+    """The random calls of one reference post_physics_step(), served from a scripted queue: each entry holds the (lower, upper, shape) the
+    call must come with and the uniforms in [0, 1) it is answered from.  A call that does not match its entry, or an entry left over,
+    fails the generation: a draw attributed to the wrong call cannot go unnoticed."""
+
+    def __init__(self):
+        self.queue = []
+
+    def expect(self, lower, upper, shape, u):
+        shape = tuple(int(k) for k in shape)
+        self.queue.append((float(lower), float(upper), shape, torch.as_tensor(np.asarray(u, dtype=np.float32)).reshape(shape)))
+
+    def _next(self, lower, upper, shape):
+        assert self.queue, f"unscripted random call ({lower}, {upper}, {tuple(shape)})"
+        lo, hi, shp, u = self.queue.pop(0)
+        assert (float(lower), float(upper), tuple(shape)) == (lo, hi, shp), f"random call ({lower}, {upper}, {tuple(shape)}) where ({lo}, {hi}, {shp}) was scripted"
+        return u
+
+    def rand_float(self, lower, upper, shape, device):   # torch_rand_float (isaacgym torch_utils): (upper - lower) * rand + lower in float32
+        return (upper - lower) * self._next(lower, upper, shape) + lower
+
+    def randint_like(self, t, high):   # the build's convention for an integer draw: floor(u * high), clipped to high - 1
+        return torch.clamp(torch.floor(self._next(0, high, t.shape) * high), max=high - 1).to(t.dtype)
+
+
+# what a row of a reset-family case is built to do: (curriculum branch, reset cause); 16 kinds, dealt round robin over the rows
+RESET_KINDS = (("up", "timeout"), ("down", "tilt"), ("neither", "contact"), ("wrap", "timeout"), ("clip", "tilt"), ("idle", None),
+               ("up", "tilt"), ("down", "contact"), ("neither", "timeout"), ("wrap", "contact"), ("clip", "timeout"), ("time", None),
+               ("post", "tilt"), ("idle", None), ("down_small", "tilt"), ("neither_small", "contact"))
+
+
+def reset_uniforms(seed, N, step, nd):
+    """The build's draws for global envs 0 .. N-1 at `step`: gro_rand(seed, env, step, stream, item) of oracle/philox.h through the
+    oracle library (oracle.binding.uniforms), streams and items as reset_env, resample_commands, the push and the curriculum use them."""
+    from oracle.binding import uniforms
+    return {name: uniforms(seed, range(N), step, name, items) for name, items in
+            (("RESET_DOF", nd), ("RESET_ROOT", 9), ("CMD_TIME", 3), ("CMD_RESET", 3), ("PUSH", 2), ("CURRICULUM", 1))}
+
+
+def drawn_commands(env, u):
+    """_resample_commands' result for the uniforms u (n, 3), in float32 like the reference."""
+    r = env.command_ranges
+    u = torch.as_tensor(u)
+    c = torch.stack([(r["lin_vel_x"][1] - r["lin_vel_x"][0]) * u[:, 0] + r["lin_vel_x"][0],
+                     (r["lin_vel_y"][1] - r["lin_vel_y"][0]) * u[:, 1] + r["lin_vel_y"][0],
+                     (r["ang_vel_yaw"][1] - r["ang_vel_yaw"][0]) * u[:, 2] + r["ang_vel_yaw"][0]], 1)
+    c[:, :2] *= (torch.norm(c[:, :2], dim=1) > 0.1).unsqueeze(1)
+    return c
+
+
+def deal_reset_kinds(env, U, N):
+    """A kind per row: RESET_KINDS round robin, except that a row whose time-based draw falls below the 0.1 norm resamples by time and a
+    row whose reset draw does resets -- the draws belong to the env index, so the rows that can show `> 0.1` zeroing are given."""
+    raw_norm = lambda u: torch.norm(torch.stack([2.0 * torch.as_tensor(u[:, 0]) - 1.0, 1.0 * torch.as_tensor(u[:, 1]) - 0.5], 1), dim=1)
+    assert env.command_ranges["lin_vel_x"] == [-1.0, 1.0] and env.command_ranges["lin_vel_y"] == [-0.5, 0.5]
+    t_small, r_small = raw_norm(U["CMD_TIME"]) < 0.1, raw_norm(U["CMD_RESET"]) < 0.1
+    kinds = [RESET_KINDS[i % 16] for i in range(N)]
+    for i in range(N):
+        if t_small[i] and r_small[i]:
+            kinds[i] = ("post", "tilt")
+        elif t_small[i] and kinds[i][0] not in ("time", "post"):
+            kinds[i] = ("time", None)
+        elif r_small[i] and kinds[i][1] is None:
+            kinds[i] = RESET_KINDS[i % 5]
+    return kinds
+
+
+def reset_family_state(env, g, body_names, N, kinds, U, tcfg, ter):
+    """Synthetic post-physics state in which row i does what kinds[i] says.  Heightfield (ter given): levels, origins, positions at a
+    chosen distance from the origin and commands on the chosen side of every curriculum threshold, each scan point 5e-4 cells from a
+    cell edge.  Every row: non-zero action / velocity history, timers, contact history and episode sums, so that reset_idx's clears show."""
+    from isaacgym.torch_utils import quat_from_euler_xyz
+    nd = env.num_dof
+    randomize_state(env, g, body_names, N, 0)
+    # the arbitrary inputs on a coarse dyadic grid (short mantissas: the fixture compresses to a third); thresholds keep their side
+    for name, step in (("dof_vel", 2), ("torques", 1), ("last_actions", 16), ("last_last_actions", 16), ("last_dof_vel", 2), ("avg_feet_contact_force", 1),
+                       ("avg_feet_speed_xyz", 16), ("feet_air_time", 64), ("feet_land_time", 64), ("base_heights_offset", 64), ("contact_forces", 1024)):
+        t = getattr(env, name)
+        t[:] = torch.round(t * step) / step
+    env.dof_pos[:] = torch.round(env.dof_pos * 64) / 64
+    env.root_states[:, 7:13] = torch.round(env.root_states[:, 7:13] * 16) / 16
+    env.rigid_body_states[:, :, 7:10] = torch.round(env.rigid_body_states[:, :, 7:10] * 16) / 16
+    env.actions = env.clip_actions(torch.round(env.actions * 16) / 16)
+    env._get_env_origins()                      # terrain_types, terrain_origins, max_terrain_level; the plane: the grid of origins
+    term = [int(i) for i in env.termination_contact_indices]
+    env.contact_forces[:, term] = 0
+    u = lambda *shape: torch.rand(*shape, generator=g)
+    t_cmd = drawn_commands(env, U["CMD_TIME"])  # what a time-based resample of this step gives the row
+    for i, (branch, cause) in enumerate(kinds):
+        # episode length: 1000 -> 1001 times out; 499 / 999 -> a multiple of the resampling interval
+        ep = int(torch.randint(0, 990, (1,), generator=g))
+        ep = 498 if ep == 499 else ep
+        if cause == "timeout":
+            ep = 1000
+        elif branch == "post":
+            ep = 499
+        elif branch == "time":
+            ep = 499 if (i // 16) % 2 == 0 else 999
+        env.episode_length_buf[i] = ep
+        yaw = (u(1) * 2 - 1) * 3.14
+        if cause == "tilt":                     # |g_z| = cos(1.3) = 0.267 < 0.33
+            env.root_states[i, 3:7] = quat_from_euler_xyz(torch.zeros(1), torch.full((1,), 1.3 if i % 2 else -1.3), yaw)[0]
+        elif branch == "idle" and i % 32 == 5:  # |g_z| = cos(1.2) = 0.362: tilted, not reset
+            env.root_states[i, 3:7] = quat_from_euler_xyz(torch.zeros(1), torch.full((1,), 1.2), yaw)[0]
+        else:
+            env.root_states[i, 3:7] = rand_quat(1, g, tilt=0.4)[0]
+        if cause == "contact":
+            env.contact_forces[i, term[i % len(term)], 2] = 5.0
+        # commands going in (norm, then a direction), and the distance from the env origin
+        ang = u(1) * 6.28
+        lvl = 1 + i % 8
+        if branch in ("up", "wrap"):
+            n, dist, lvl = 0.3 + 0.7 * u(1), 4.5 + 2.0 * u(1), (9 if branch == "wrap" else lvl)
+        elif branch in ("down", "clip"):
+            n = 0.5 + 0.5 * u(1)
+            dist, lvl = (0.1 + 0.6 * u(1)) * 4.0, (0 if branch == "clip" else lvl)
+        elif branch == "neither":
+            n = torch.zeros(1) if i % 2 else 0.15 + 0.15 * u(1)
+            dist = 10.0 * n + 0.3 + 0.6 * u(1)
+        elif branch == "down_small":
+            n = 0.04 + 0.05 * u(1)
+            dist = 5.0 * n
+        elif branch == "neither_small":
+            n, dist = 0.04 + 0.05 * u(1), 1.5 + u(1)
+        elif branch == "post":                  # resets on a step where it also resamples by time: the curriculum sees the NEW commands
+            tn = torch.norm(t_cmd[i, :2])
+            if tn > 0.1:                        # old commands zero (never down), new ones make it move down
+                n, dist = torch.zeros(1), torch.clamp(5.0 * tn, max=3.0).reshape(1)
+            else:                               # old commands would move it down, the new (zeroed) ones do not
+                n, dist = torch.full((1,), 0.8), torch.full((1,), 2.0)
+        else:                                   # idle / time: anything
+            n, dist = (torch.zeros(1) if i % 4 == 0 else 1.1 * u(1)), 6.0 * u(1)
+        env.commands[i, 0], env.commands[i, 1] = float(n * torch.cos(ang)), float(n * torch.sin(ang))
+        if ter is None:
+            env.root_states[i, 0:2] += env.env_origins[i, 0:2]
+            continue
+        env.terrain_levels[i] = lvl
+        env.env_origins[i] = env.terrain_origins[lvl, env.terrain_types[i]]
+        while True:
+            a = u(1) * 6.28
+            env.root_states[i, 0:2] = env.env_origins[i, 0:2] + dist * torch.cat([torch.cos(a), torch.sin(a)])
+            if scan_edge_margin(env, tcfg, i) >= 5e-4:
+                break
+    if ter is not None:
+        stand_on_terrain(env, g, tcfg, ter, N)
+    else:
+        torso = int(env.torso_indices[0])
+        env.rigid_body_states[:, :, 0:3] = env.root_states[:, None, 0:3]
+        env.rigid_body_states[:, env.feet_indices, 2] = torch.rand(N, 2, generator=g) * 0.25
+        env.rigid_body_states[:, torso, 3:7] = env.root_states[:, 3:7]
+    feet = env.feet_indices                     # (of the feet's positions the step reads z alone)
+    env.rigid_body_states[:, feet, 0:2] = torch.round(env.rigid_body_states[:, feet, 0:2])
+    env.rigid_body_states[:, feet, 2] = torch.round(env.rigid_body_states[:, feet, 2] * 1024) / 1024
+    if nd == 32:
+        full_body_link_orientations(env)
+    for name in env.episode_sums:
+        env.episode_sums[name] = torch.round((torch.rand(N, generator=g) - 0.3) * 2.0 * 4) / 4
+
+
+def reset_family_margins(env, kinds, U, tcfg, rows, curriculum):
+    """The conditions of the fixture, in float64 on the float32 state: no row within 1e-3 (relative) of a threshold the step compares
+    against, every floor(u * high) 1e-4 from an integer, every scan point 5e-4 cells from a cell edge.  Returns (violations, counts of
+    the rows `rows` per branch)."""
+    N = env.num_envs
+    bad, cnt = [], {}
+
+    def count(name, mask):
+        cnt[name] = int(np.asarray(mask)[rows].sum())
+
+    def off(name, value, thr, rel=1e-3):
+        value, thr = np.asarray(value, dtype=np.float64), np.asarray(thr, dtype=np.float64)
+        if (np.abs(value - thr) <= rel * np.abs(thr)).any():
+            bad.append(name)
+    ep1 = env.episode_length_buf.numpy() + 1
+    by_time = ep1 % int(env.cfg.commands.resample_command_interval) == 0
+    t_raw, r_raw = (np.stack([2.0 * U[k][:, 0].astype(np.float64) - 1.0, U[k][:, 1].astype(np.float64) - 0.5], 1) for k in ("CMD_TIME", "CMD_RESET"))
+    cmd = env.commands[:, :2].double().numpy().copy()
+    t_norm, r_norm = np.linalg.norm(t_raw, axis=1), np.linalg.norm(r_raw, axis=1)
+    cmd[by_time] = t_raw[by_time] * (t_norm[by_time] > 0.1)[:, None]        # the commands the reward and the curriculum see
+    cn = np.linalg.norm(cmd, axis=1)
+    q = env.root_states[:, 3:7].double().numpy()
+    gz = 1.0 - 2.0 * (q[:, 0] ** 2 + q[:, 1] ** 2) / (q ** 2).sum(1)
+    causes = np.array([k[1] or "" for k in kinds])
+    resets = causes != ""
+    off("|g_z| at 0.33", np.abs(gz), 0.33)
+    assert ((np.abs(gz) < 0.33) == (causes == "tilt")).all() and ((ep1 > 1000) == (causes == "timeout")).all()
+    off("time-drawn commands at the 0.1 norm", t_norm[by_time], 0.1)
+    off("reset-drawn commands at the 0.1 norm", r_norm[resets], 0.1)
+    off("commands at the 0.1 norm", cn[cn > 0], 0.1)
+    for c in ("timeout", "tilt", "contact"):
+        count("reset by " + c, causes == c)
+    count("no reset", ~resets & ~by_time)
+    count("time resample only", ~resets & by_time)
+    count("reset and time resample", resets & by_time)
+    count("time draw below 0.1", by_time & (t_norm < 0.1))
+    count("time draw above 0.1", by_time & (t_norm > 0.1))
+    count("reset draw below 0.1", resets & (r_norm < 0.1))
+    count("reset draw above 0.1", resets & (r_norm > 0.1))
+    if env.custom_origins:
+        for i in range(N):
+            if scan_edge_margin(env, tcfg, i) < 5e-4:
+                bad.append("scan point at a cell edge")
+    if curriculum:
+        d = np.linalg.norm(env.root_states[:, :2].double().numpy() - env.env_origins[:, :2].double().numpy(), axis=1)
+        T = float(env.max_episode_length_s)
+        off("distance at env_length / 2", d, env.terrain.env_length / 2)
+        off("distance at |cmd| T / 2", d[cn > 0], cn[cn > 0] * T * 0.5)
+        up = d > env.terrain.env_length / 2
+        down = (d < cn * T * 0.5) & ~up
+        old = np.linalg.norm(env.commands[:, :2].double().numpy(), axis=1)
+        down_old = (d < old * T * 0.5) & ~up
+        lv = env.terrain_levels.numpy()
+        top = int(env.max_terrain_level) - 1
+        uc = U["CURRICULUM"][:, 0].astype(np.float64) * int(env.max_terrain_level)
+        if (np.abs(uc - np.rint(uc)) < 1e-4).any():
+            bad.append("floor(u * high) at an integer")
+        count("up", resets & up & (lv < top))
+        count("down", resets & down & (lv > 0))
+        count("neither", resets & ~up & ~down)
+        count("wrap from the top level", resets & up & (lv == top))
+        count("clip at level 0", resets & down & (lv == 0))
+        count("curriculum commands below 0.1", resets & (cn > 0) & (cn < 0.1))
+        count("curriculum commands above 0.1", resets & (cn > 0.1))
+        count("down with commands below 0.1", resets & down & (cn < 0.1))
+        count("decision differs on the pre-resample commands", resets & by_time & (down != down_old))
+    return bad, cnt
+
+
+def reset_family_case(N, robot, seed, step, ter=None, tcfg=None, curriculum=True, init_done=True, dr=True, rows=slice(None),
+                      strict=False, kinds=None, state_step=None, build_seed=1):
+    """One live reference post_physics_step() -- reset_idx NOT stubbed -- with the build's draws injected.  Returns (record, kinds), or
+    None when a condition of the fixture (reset_family_margins) does not hold for this step's draws."""
+    import legged_gym.envs.base.legged_robot as LR
+    env, g, body_names = make_ref_env(N, seed, terrain_obj=ter, robot=robot)
+    nd = env.num_dof
+    if ter is None:
+        env.cfg.terrain.mesh_type = "plane"
+    env.cfg.terrain.curriculum = bool(curriculum and ter is not None)
+    env.cfg.domain_rand.push_robots = True
+    env.cfg.domain_rand.randomize_init_dof_pos = env.cfg.domain_rand.randomize_init_base_velocity = bool(dr)
+    assert not env.cfg.commands.curriculum and not env.cfg.commands.heading_command and env.cfg.env.send_timeouts
+    env.cfg.noise.add_noise = False             # (the observation noise is pipeline.npz's subject; without it obs repeats pri_obs' first columns)
+    U = reset_uniforms(build_seed, N, step, nd)
+    if kinds is None:
+        kinds = deal_reset_kinds(env, U, N)
+    # (state_step: the state of another case, whose step's draws placed the rows that reset while they resample by time)
+    reset_family_state(env, g, body_names, N, kinds, U if state_step is None else reset_uniforms(build_seed, N, state_step, nd), tcfg, ter)
+    bad, cnt = reset_family_margins(env, kinds, U, tcfg, rows, env.cfg.terrain.curriculum)
+    main = ["reset by timeout", "reset by tilt", "reset by contact", "no reset", "time resample only", "reset and time resample"]
+    if env.cfg.terrain.curriculum:
+        main += ["up", "down", "neither", "wrap from the top level", "clip at level 0", "curriculum commands below 0.1", "curriculum commands above 0.1"]
+    if strict:
+        main = list(cnt)
+    if bad or any(cnt[k] < 3 for k in main):
+        return None
+    inp = snapshot_inputs(env)
+    inp.update(terrain_levels=env.terrain_levels.numpy().astype(np.int32) if ter is not None else np.zeros(N, np.int32),
+               terrain_types=env.terrain_types.numpy().astype(np.int32) if ter is not None else np.zeros(N, np.int32),
+               env_origins=env.env_origins.numpy().copy(), episode_sums=np.stack([env.episode_sums[n].numpy().copy() for n in env.reward_names]))
+    # the script: the calls of post_physics_step in their order (legged_robot.py:307-334, 377-440, 650-677, 717-826)
+    S = ScriptedDraws()
+    r = env.command_ranges
+    ep1 = env.episode_length_buf + 1
+    t_ids = (ep1 % env.cfg.commands.resample_command_interval == 0).nonzero().flatten().numpy()
+    r_ids = np.array([i for i, k in enumerate(kinds) if k[1] is not None])
+
+    def resample(ids, name):
+        for k, key in enumerate(("lin_vel_x", "lin_vel_y", "ang_vel_yaw")):
+            S.expect(r[key][0], r[key][1], (len(ids), 1), U[name][ids, k])
+    resample(t_ids, "CMD_TIME")
+    pushed = step % int(env.cfg.domain_rand.push_interval) == 0
+    if pushed:
+        S.expect(-env.cfg.domain_rand.max_push_vel_xy, env.cfg.domain_rand.max_push_vel_xy, (N, 2), U["PUSH"])
+    n = len(r_ids)
+    if env.cfg.terrain.curriculum and init_done:
+        S.expect(0, env.max_terrain_level, (n,), U["CURRICULUM"][r_ids, 0])
+    if dr:
+        S.expect(0.5, 1.5, (n, nd), U["RESET_DOF"][r_ids])
+    if env.custom_origins:
+        S.expect(-1.0, 1.0, (n, 2), U["RESET_ROOT"][r_ids, 0:2])
+    S.expect(-2 * np.pi, 2 * np.pi, (n, 1), U["RESET_ROOT"][r_ids, 2:3])
+    if dr:
+        S.expect(-0.5, 0.5, (n, 6), U["RESET_ROOT"][r_ids, 3:9])
+    resample(r_ids, "CMD_RESET")
+    env.common_step_counter = step - 1          # post_physics_step counts it up before the push test
+    env.init_done = bool(init_done)
+    orig = (LR.torch_rand_float, torch.randint_like)
+    LR.torch_rand_float, torch.randint_like = S.rand_float, S.randint_like
+    try:
+        env.post_physics_step()
+    finally:
+        LR.torch_rand_float, torch.randint_like = orig
+    assert not S.queue, f"{len(S.queue)} scripted draws were never asked for"
+    assert env.common_step_counter == step and sorted(env.reset_buf.nonzero().flatten().tolist()) == sorted(r_ids.tolist())
+    ex = env.extras["episode"]
+    outd = dict(dof_pos=env.dof_pos.numpy().copy(), dof_vel=env.dof_vel.numpy().copy(), root=env.root_states.numpy().copy(),
+                commands=env.commands.numpy().copy(), env_origins=env.env_origins.numpy().copy(),
+                terrain_levels=env.terrain_levels.numpy().astype(np.int32) if ter is not None else np.zeros(N, np.int32),
+                reset=env.reset_buf.numpy().astype(bool), time_out=env.time_out_buf.numpy().copy(), episode_length=env.episode_length_buf.numpy().copy(),
+                pri_obs=torch.clip(env.pri_obs_buf, -100, 100).numpy().copy(), obs=torch.clip(env.obs_buf, -100, 100).numpy().copy(),
+                rew=env.rew_buf.numpy().copy(), last_actions=env.last_actions.numpy().copy(), last_last_actions=env.last_last_actions.numpy().copy(),
+                last_dof_vel=env.last_dof_vel.numpy().copy(), feet_air_time=env.feet_air_time.numpy().copy(),
+                feet_land_time=env.feet_land_time.numpy().copy(), feet_contact=env.feet_contact.numpy().astype(bool),
+                episode_sums=np.stack([env.episode_sums[n].numpy().copy() for n in env.reward_names]),
+                extras_rew=np.array([float(ex["rew_" + n]) for n in env.reward_names], dtype=np.float32),
+                extras_time_outs=env.extras["time_outs"].numpy().copy())
+    assert set(ex) - {"terrain_level"} == {"rew_" + n for n in env.reward_names}
+    if env.cfg.terrain.curriculum:
+        outd["extras_terrain_level"] = np.float32(ex["terrain_level"])
+    else:
+        assert "terrain_level" not in ex
+    rec = {"in_" + k: v for k, v in inp.items()}
+    rec.update({"out_" + k: v for k, v in outd.items()})
+    rec.update({"u_" + k: v for k, v in U.items()})
+    rec.update(step_seed_offset=np.array([step, build_seed, 0], dtype=np.int64),   # common_step_counter, seed, env_offset of the build's handle
+               reward_names=np.array(env.reward_names), branch_names=np.array(list(cnt)), branch_counts=np.array([cnt[k] for k in cnt], dtype=np.int32))
+    return rec, kinds
+
+
+def gen_reset_family(out):
+    """tests/golden/reset_family.npz: the reference's LIVE reset path -- reset_idx and what it calls (the terrain-curriculum move,
+    _reset_dofs, _reset_root_states, _resample_commands), the time-based resample, _push_robots, the buffer clears of both classes, the
+    extras["episode"] means -- through one post_physics_step() per case, and _get_env_origins.
+
+    The reference draws from torch's global generators, which the build cannot reproduce; so the build's own draws go INTO the
+    reference: torch_rand_float (as legged_robot.py sees it) and torch.randint_like are replaced for the duration of the step by a
+    scripted queue (ScriptedDraws) of the uniforms gro_rand(seed, env, step = common_step_counter, stream, item) of oracle/philox.h --
+    RESET_DOF item j, RESET_ROOT 0-8, CMD_TIME / CMD_RESET 0-2, PUSH 0-1, CURRICULUM 0 -- computed for every env by the oracle library
+    and indexed with the env ids of each call.  randint_like returns floor(u * high) clipped to high - 1: that is the build's convention,
+    the reference's own integer generator is not reproducible.  The uniforms are stored; the tests check them against today's gro_rand.
+
+    Cases (64 envs unless noted; rows are built so that every branch is taken by several rows, RESET_KINDS):
+      curr       heightfield (the raster of terrain.npz), curriculum on, init_done
+      push       the same state on a step where the push fires; pushed rows that reset lose the push to the reset
+      nodr       the same state with randomize_init_dof_pos / randomize_init_base_velocity off
+      init       the same state with init_done False, on the draws of the build's first reset_all: the levels must not move
+      plane      mesh_type 'plane': grid origins, no xy offset, no curriculum
+      shard      128 envs; the tests run rows 64-127 as a handle with env_offset 64 of 128
+      full_body  the 32-DOF robot (build_full_body_cfg)
+      origins    _get_env_origins alone: terrain_types for several (num_envs, 20), the plane grid
+    The conditions under which the cases compare without excluding a row are asserted HERE (reset_family_margins): no row within 1e-3
+    of a threshold, floor(u * high) 1e-4 from an integer, scan points 5e-4 cells from a cell edge, at least 3 rows per branch."""
+    from legged_gym.utils.terrain import Terrain
+    from legged_gym.envs.base.legged_robot_config import LeggedRobotCfg
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if repo not in sys.path:
+        sys.path.insert(0, repo)
+    tcfg = LeggedRobotCfg.terrain()
+    tcfg.mesh_type = "heightfield"
+    np.random.seed(1)
+    ter = Terrain(tcfg, 64)          # the raster of terrain.npz
+    data, arrays = {}, {}
+
+    def first(steps, **kw):
+        for step in steps:
+            got = reset_family_case(step=step, **kw)
+            if got is not None:
+                return got
+        raise AssertionError("no step whose draws meet the fixture's conditions")
+
+    def store(case, rec, like=None, same_state=False):
+        """The storage layout (tests/test_reset_golden.py load_case undoes it; a zip member costs ~250 bytes, a case has ~50 arrays):
+          <case>_f32, <case>_f32_names   every per-row float32 array of the case, one row of the matrix per column of the array ("name:2x3"; "name:T24": a (24, rows) array as it is)
+          <case>_i32, <case>_i32_names   the same for the per-row integer and boolean arrays ("name:2:|b1")
+          <case>_same                    "name=@other" / "name=@other[:k]": an array equal to one already stored for this case or for the
+                                         case `like` (the cases that share curr's state; obs = pri_obs' leading columns without noise; ...)
+          <case>_<name>                  everything else"""
+        rows = len(rec["in_root"])
+        names, cols, inames, icols, same = [], [], [], [], []
+        for k, v in rec.items():
+            v = np.asarray(v)
+            twin = None
+            for n, w in arrays.items() if v.size > 16 else ():
+                if not (n.startswith(case + "_") or (like and n.startswith(like + "_"))) or w.dtype != v.dtype or w.ndim != v.ndim:
+                    continue
+                if w.shape == v.shape and np.array_equal(w, v):
+                    twin = "@" + n
+                elif v.ndim == 2 and w.shape[0] == v.shape[0] and w.shape[1] > v.shape[1] and np.array_equal(w[:, :v.shape[1]], v):
+                    twin = f"@{n}[:{v.shape[1]}]"
+                if twin:
+                    break
+            if twin is not None:
+                same.append(k + "=" + twin)
+                continue
+            arrays[case + "_" + k] = v
+            if v.dtype == np.float32 and v.ndim >= 1 and v.shape[0] == rows:
+                names.append(k + ":" + "x".join(str(n) for n in v.shape[1:]))
+                cols.append(v.reshape(rows, -1).T)
+            elif v.dtype == np.float32 and v.ndim == 2 and v.shape[1] == rows:      # (terms, rows): the episode sums
+                names.append(k + ":T" + str(v.shape[0]))
+                cols.append(v)
+            elif v.dtype.kind in "iub" and v.ndim >= 1 and v.shape[0] == rows:
+                inames.append(k + ":" + "x".join(str(n) for n in v.shape[1:]) + ":" + v.dtype.str)
+                icols.append(v.reshape(rows, -1).T.astype(np.int32))
+            else:
+                data[case + "_" + k] = v
+        assert not same_state or all(any(a.startswith(k + "=") for a in same) for k in rec if k.startswith("in_")), case   # the same state: stored once
+        data[case + "_same"] = np.array(same)
+        for tag, nm, cl in (("_f32", names, cols), ("_i32", inames, icols)):
+            if cl:
+                data[case + tag], data[case + tag + "_names"] = np.concatenate(cl), np.array(nm)
+    plain = [s for s in range(3, 4000) if s % 500]
+    curr, kinds = first(plain, N=64, robot="gr1t1_lower_limb", seed=51, ter=ter, tcfg=tcfg, strict=True)
+    store("curr", curr)
+    step = int(curr["step_seed_offset"][0])
+    shared = dict(N=64, robot="gr1t1_lower_limb", seed=51, ter=ter, tcfg=tcfg, kinds=kinds, state_step=step)
+    rec, _ = first(range(500, 20000, 500), **shared)
+    assert np.abs(rec["out_root"][~rec["out_reset"], 7:9] - curr["out_root"][~curr["out_reset"], 7:9]).min() > 0
+    store("push", rec, "curr", True)
+    rec, _ = first([step], dr=False, **shared)
+    store("nodr", rec, "curr", True)
+    # (the build takes init_done = False in reset_all alone, whose draws are keyed by step 0x80000000 + the number of resets so far)
+    rec, _ = first([0x80000000], init_done=False, **shared)
+    assert np.array_equal(rec["out_terrain_levels"], rec["in_terrain_levels"]) and not np.array_equal(curr["out_terrain_levels"], curr["in_terrain_levels"])
+    store("init", rec, "curr", True)
+    rec, _ = first(plain, N=64, robot="gr1t1_lower_limb", seed=51, curriculum=False)
+    for k in ("in_dof_pos", "in_actions", "in_torques"):     # (the seed of curr: randomize_state's arrays are the same)
+        assert np.array_equal(rec[k], curr[k]), k
+    store("plane", rec, "curr")
+    rec, _ = first(plain, N=128, robot="gr1t1_lower_limb", seed=55, ter=ter, tcfg=tcfg, rows=slice(64, 128))
+    rec["step_seed_offset"][2] = 64              # rows 64-127 are stored: what a handle with env_offset 64 of 128 envs computes
+    for k in ("out_extras_rew", "out_extras_terrain_level"):   # (means over all 128 envs: a shard's statistics cover its own rows)
+        del rec[k]
+    for k, v in rec.items():
+        if k.startswith(("in_", "out_", "u_")):
+            rec[k] = np.take(v, np.arange(64, 128), axis=v.shape.index(128))
+    store("shard", rec, "curr")
+    rec, _ = first(plain, N=64, robot="gr1t1", seed=57, ter=ter, tcfg=tcfg)
+    store("full_body", rec, "curr")
+    # _get_env_origins alone (legged_robot.py:1163-1195)
+    for N in (64, 100, 4095, 4096):
+        for curriculum, max_init in ((True, 4), (False, 4)):
+            env, _, _ = make_ref_env(N, 59, terrain_obj=ter)
+            env.cfg.terrain.curriculum, env.cfg.terrain.max_init_terrain_level = curriculum, max_init
+            env._get_env_origins()
+            top = max_init if curriculum else env.cfg.terrain.num_rows - 1
+            assert int(env.terrain_levels.min()) >= 0 and int(env.terrain_levels.max()) <= top and (N < 4095 or int(env.terrain_levels.max()) == top)
+            assert env.custom_origins and torch.equal(env.env_origins, env.terrain_origins[env.terrain_levels, env.terrain_types])
+            if curriculum:
+                data[f"origins_types_{N}"] = env.terrain_types.numpy().astype(np.int16)
+    data["origins_num_cols"] = np.int64(tcfg.num_cols)
+    for N in (64, 100, 4096):
+        env, _, _ = make_ref_env(N, 59)
+        env.cfg.terrain.mesh_type = "plane"
+        env._get_env_origins()
+        assert not env.custom_origins
+        data[f"origins_grid_{N}"] = env.env_origins.numpy().T.copy()      # (3, N): a coordinate per row
+    path = os.path.join(out, "reset_family.npz")
+    np.savez_compressed(path, **data)
+    assert os.path.getsize(path) <= os.path.getsize(os.path.join(out, "pipeline.npz")), "reset_family.npz outgrew the largest fixture"
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     install_stub()
@@ -887,6 +1354,7 @@ def main():
     gen_trimesh_tiles(OUT)
     gen_config(OUT)
     gen_ppo(OUT)
+    gen_reset_family(OUT)
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))
 
