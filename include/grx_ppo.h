@@ -131,6 +131,34 @@ int grx_mlp_weight_grad_bf16(int M, int N, int K, const float* dZ, const float* 
 int grx_mlp_policy_head(int M, int K, int A, const float* X, const float* W, const float* bias, const float* std,
                         const float* eps, float* actions, float* logp, float* mu, float* sigma, void* stream);
 
+/* Empirical observation normalisation (rsl_rl 2.x `empirical_normalization`; rl/normalizer.py): the running mean and
+ * variance of every column of an observation tensor x [rows][cols], and y = (x - mean) / (std + eps).  State per tensor, all on the
+ * device: count (ONE int64: a float count stops being exact after 2^24 samples), mean / var / std [cols] fp32.  A training step is three
+ * launches -- moments, merge, apply --, an evaluation step the third alone.  Deterministic: no atomics, every sum's order is a function
+ * of (rows, cols) / of n_partials.  The state is written by the merge launch only (one block), never while another launch reads it.
+ *   grx_obs_norm_moments: per slab of rows (the slab geometry is a function of (rows, cols) only) one CENTRED triple per column,
+ *                         partials [slab][3][cols] = { n, mean, M2 = sum (x - mean)^2 }: the slab's mean is formed before its squares
+ *                         are summed (never E[x^2] - mean^2).  `partials`: grx_obs_norm_partials_size(rows, cols) floats (0: invalid).
+ *   grx_obs_norm_merge:   merges n_partials triples in index order (Chan et al.: n = na + nb, d = mb - ma, m = ma + d nb / n,
+ *                         M2 = M2a + M2b + d^2 na nb / n), then the running update in place, with n, m, v = M2 / n of the merged batch:
+ *                           count += n; rate = n / count; delta = m - mean; mean += rate * delta;
+ *                           var += rate * (v - var + delta * (m - mean_new)); std = sqrt(var)
+ *                         Triple p starts at partials + p * stride floats (stride 0: packed, 3 * cols): the same kernel consumes the
+ *                         slab partials of one rank and the all_gathered triples of several ranks packed beside another tensor's.
+ *   grx_obs_norm_combine: the same merge without a state: out [3][cols] = the one triple of all n_partials (a rank's contribution)
+ *   grx_obs_norm_apply:   y [rows][cols] = (x - mean) / (std + eps); reads the state, writes y only (y may be x)
+ *   grx_obs_norm_step:    moments, merge (packed partials) and apply of one training step behind one call: the same three launches
+ * rows <= 2^24 per call (a triple carries n as a float).  Return 0, or negative for invalid sizes / NULL pointers (nothing is
+ * launched) / a failed launch. */
+int grx_obs_norm_partials_size(int rows, int cols);
+int grx_obs_norm_moments(int rows, int cols, const float* x, float* partials, void* stream);
+int grx_obs_norm_merge(int n_partials, int cols, int stride, const float* partials, long long* count, float* mean, float* var, float* std,
+                       void* stream);
+int grx_obs_norm_combine(int n_partials, int cols, const float* partials, float* out, void* stream);
+int grx_obs_norm_apply(int rows, int cols, const float* x, const float* mean, const float* std, float eps, float* y, void* stream);
+int grx_obs_norm_step(int rows, int cols, const float* x, float* partials, long long* count, float* mean, float* var, float* std, float eps,
+                      float* y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

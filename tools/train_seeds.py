@@ -3,7 +3,8 @@ PPO with the reference's hyper-parameters, N seeds x 1500 iterations.  Reports r
 over the seeds, episode length, wall-clock and the training env-steps/s, plus which step kernel ran (grx_layout).
     python tools/train_seeds.py [iterations=1500] [seeds=3] [envs=4096] [terrain=plane] [task=GR1T1]   ->  gpurun_out/learning_curve_<terrain>_<envs>.json
 (task GR1T1_full_body: the 32-DOF robot of BASELINE.json's fifth configuration on the tree kernel -> ..._full_body_<terrain>_<envs>.json)
-GRX_TRAIN_PRECISION=bf16: PPO's hidden layers in bf16 (the --precision flag) -> learning_curve_<terrain>_bf16_<envs>.json"""
+GRX_TRAIN_PRECISION=bf16: PPO's hidden layers in bf16 (the --precision flag) -> learning_curve_<terrain>_bf16_<envs>.json
+GRX_TRAIN_OBS_NORM=1: empirical observation normalisation (the --empirical_normalization flag) -> learning_curve_<terrain>_obs_norm_<envs>.json"""
 import contextlib, io, json, os, sys, time
 sys.path.insert(0, ".")
 import numpy as np
@@ -16,7 +17,8 @@ task = sys.argv[5] if len(sys.argv) > 5 else "GR1T1"
 full = task == "GR1T1_full_body"
 gr1t2 = task == "GR1T2"   # (BASELINE.json's fourth configuration: one rank's 4096-env shard of the 32768)
 precision = os.environ.get("GRX_TRAIN_PRECISION")
-tag = ("full_body_" if full else "gr1t2_" if gr1t2 else "") + terrain + (f"_{precision}" if precision else "")
+obs_norm = os.environ.get("GRX_TRAIN_OBS_NORM") == "1"
+tag = ("full_body_" if full else "gr1t2_" if gr1t2 else "") + terrain + (f"_{precision}" if precision else "") + ("_obs_norm" if obs_norm else "")
 os.makedirs("gpurun_out", exist_ok=True)
 runs = []
 for seed in range(int(os.environ.get("GRX_TRAIN_FIRST_SEED", "1")), int(os.environ.get("GRX_TRAIN_FIRST_SEED", "1")) + seeds):
@@ -24,7 +26,7 @@ for seed in range(int(os.environ.get("GRX_TRAIN_FIRST_SEED", "1")), int(os.envir
     from wiki_grx_gym_amd.envs import GR1T1Cfg, GR1T1CfgPPO, GR1T1FullBodyCfg, GR1T1FullBodyCfgPPO, GR1T2Cfg, GR1T2CfgPPO
     from wiki_grx_gym_amd.utils import get_args, task_registry
     args = get_args(["--task", task, "--headless", "--num_envs", str(envs), "--seed", str(seed), "--max_iterations", str(iters)]
-                    + (["--precision", precision] if precision else []))
+                    + (["--precision", precision] if precision else []) + (["--empirical_normalization"] if obs_norm else []))
     cfg = GR1T1FullBodyCfg() if full else GR1T2Cfg() if gr1t2 else GR1T1Cfg()
     cfg.terrain.mesh_type = terrain
     if os.environ.get("GRX_TRAIN_ONLY_POSITIVE") == "1":   # (diagnosis of the 32-DOF task: legged_robot.py:251-252's clip of the total reward at zero, off in the GR1T1 configs)
@@ -72,7 +74,7 @@ for seed in range(int(os.environ.get("GRX_TRAIN_FIRST_SEED", "1")), int(os.envir
     print(json.dumps({k: v for k, v in res.items() if not isinstance(v, list)}), flush=True)
     r_ = np.array([r["reward_at_end"] for r in runs]); l_ = np.array([r["episode_length_at_end"] for r in runs]); w_ = np.array([r["wall_s"] for r in runs])
     summary = {"task": ("GR1T1 full body (32 DOF), " if full else "GR1T2 (lower limb), " if gr1t2 else "GR1T1 (lower limb), ") + ("flat plane" if terrain == "plane" else terrain), "num_envs": envs, "iterations": iters, "seeds": len(runs),
-               "step_kernel": layout, "precision": precision or "fp32", "reward_at_end_mean": float(r_.mean()), "iterations_run": iters, "reward_at_end_sd": float(r_.std(ddof=1)) if len(runs) > 1 else None,
+               "step_kernel": layout, "precision": precision or "fp32", "empirical_normalization": obs_norm, "reward_at_end_mean": float(r_.mean()), "iterations_run": iters, "reward_at_end_sd": float(r_.std(ddof=1)) if len(runs) > 1 else None,
                "episode_length_mean": float(l_.mean()), "wall_s_mean": float(w_.mean()), "wall_s_sd": float(w_.std(ddof=1)) if len(runs) > 1 else None,
                "note": "reward_at_end = mean of Train/mean_reward over the last 100 iterations; PPO hyper-parameters of the registered GR1T1 task "
                        "(gr1t1_lower_limb_config.py; the full-body task: this build's GR1T1FullCfgPPO); no reference curve exists to compare with (Isaac Gym is absent: BASELINE.md)",

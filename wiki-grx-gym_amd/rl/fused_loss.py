@@ -53,6 +53,19 @@ def load_ppo_library():
         lib.grx_ppo_step_tail.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.grx_ppo_step_tail_blocks.restype = C.c_int
         lib.grx_ppo_step_tail_blocks.argtypes = [C.c_void_p]
+        # the observation normaliser (rl/normalizer.py)
+        lib.grx_obs_norm_partials_size.restype = C.c_int
+        lib.grx_obs_norm_partials_size.argtypes = [C.c_int, C.c_int]
+        lib.grx_obs_norm_moments.restype = C.c_int
+        lib.grx_obs_norm_moments.argtypes = [C.c_int, C.c_int, fp, fp, C.c_void_p]
+        lib.grx_obs_norm_merge.restype = C.c_int
+        lib.grx_obs_norm_merge.argtypes = [C.c_int, C.c_int, C.c_int] + [fp] * 5 + [C.c_void_p]
+        lib.grx_obs_norm_combine.restype = C.c_int
+        lib.grx_obs_norm_combine.argtypes = [C.c_int, C.c_int, fp, fp, C.c_void_p]
+        lib.grx_obs_norm_apply.restype = C.c_int
+        lib.grx_obs_norm_apply.argtypes = [C.c_int, C.c_int, fp, fp, fp, C.c_float, fp, C.c_void_p]
+        lib.grx_obs_norm_step.restype = C.c_int
+        lib.grx_obs_norm_step.argtypes = [C.c_int, C.c_int] + [fp] * 6 + [C.c_float, fp, C.c_void_p]
         _LIB = lib
     return _LIB
 

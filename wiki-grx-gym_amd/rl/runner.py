@@ -19,6 +19,7 @@ import torch
 import torch.distributed as dist
 
 from .modules import ActorCriticMLP
+from .normalizer import EmpiricalNormalization, normalize_step
 from .ppo import PPO
 from .storage import RolloutStorage  # noqa: F401
 
@@ -63,6 +64,15 @@ class OnPolicyRunner:
         self.exact_resume = bool(self.cfg.get("exact_resume", False))
         if self.exact_resume and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise NotImplementedError("exact_resume: one process only (with more ranks every rank holds its own env shard)")
+        # empirical observation normalisation: running mean / variance of the actor's and -- when the env has privileged
+        # observations -- the critic's inputs; what the policy acts on, what the storage keeps and what compute_returns gets are the
+        # normalised tensors.  Not a config key either (`--empirical_normalization` or an assignment to train_cfg.runner sets it)
+        self.empirical_normalization = bool(self.cfg.get("empirical_normalization", False))
+        self.obs_normalizer = self.critic_obs_normalizer = None
+        if self.empirical_normalization:
+            self.obs_normalizer = EmpiricalNormalization(env.num_obs).to(device)
+            if env.num_pri_obs is not None:
+                self.critic_obs_normalizer = EmpiricalNormalization(env.num_pri_obs).to(device)
         self._pending_state = None   # what load_train_state() restored and learn() still has to apply
         self._log_buffers = None     # learn()'s running episode reward / length and the finished episodes' deques
         self._next_iteration = None  # the iteration a save() from inside learn() resumes at
@@ -91,6 +101,17 @@ class OnPolicyRunner:
         pri = env.get_privileged_observations()
         critic_obs = pri if pri is not None else obs
         obs, critic_obs = obs.to(self.device), critic_obs.to(self.device)
+        if self.empirical_normalization:
+            # the observations learn() starts from, with the statistics as they are: every observation updates the statistics exactly once,
+            # after its env.step (a resumed run's first observations went in before the checkpoint; a fresh run's are x / 1.01)
+            self.obs_normalizer.train()
+            obs_n = self.obs_normalizer.normalize(obs)
+            if self.critic_obs_normalizer is not None:
+                self.critic_obs_normalizer.train()
+                critic_obs = self.critic_obs_normalizer.normalize(critic_obs)
+            else:
+                critic_obs = obs_n
+            obs = obs_n
         alg.actor_critic.train()
         ep_infos = []
         if pending is None:
@@ -116,6 +137,8 @@ class OnPolicyRunner:
                     obs, pri, rewards, dones, infos = env.step(actions)
                     critic_obs = pri if pri is not None else obs
                     obs, critic_obs, rewards, dones = obs.to(self.device), critic_obs.to(self.device), rewards.to(self.device), dones.to(self.device)
+                    if self.empirical_normalization:
+                        obs, critic_obs = self._normalize_step(obs, critic_obs if pri is not None else None)
                     if self.log_dir is not None:
                         if "episode" in infos:
                             ep_infos.append(infos["episode"])
@@ -150,6 +173,14 @@ class OnPolicyRunner:
             self._next_iteration = self.current_learning_iteration
             self.save(os.path.join(self.log_dir, f"model_{self.current_learning_iteration}.pt"))
         self._next_iteration = None
+
+    def _normalize_step(self, obs, pri):
+        """one env step's observations into the statistics (training mode) and back normalised: (actor input, critic input)"""
+        if pri is not None and self.critic_obs_normalizer is not None:
+            obs, pri = normalize_step([self.obs_normalizer, self.critic_obs_normalizer], [obs, pri])
+            return obs, pri
+        obs, = normalize_step([self.obs_normalizer], [obs])
+        return obs, obs
 
     def log(self, locs, width=80, pad=35):
         it = locs["it"]
@@ -194,9 +225,14 @@ class OnPolicyRunner:
         print(out)
 
     def save(self, path, infos=None):
-        torch.save({"model_state_dict": self.algorithm.actor_critic.state_dict(),
-                    "optimizer_state_dict": self.algorithm.optimizer.state_dict(),
-                    "iter": self.current_learning_iteration, "infos": infos}, path)
+        saved = {"model_state_dict": self.algorithm.actor_critic.state_dict(),
+                 "optimizer_state_dict": self.algorithm.optimizer.state_dict(),
+                 "iter": self.current_learning_iteration, "infos": infos}
+        if self.empirical_normalization:   # (rsl_rl 2.x's keys; absent otherwise: the checkpoint keeps exactly the reference's keys)
+            saved["obs_norm_state_dict"] = self.obs_normalizer.state_dict()
+            critic_norm = self.critic_obs_normalizer if self.critic_obs_normalizer is not None else self.obs_normalizer
+            saved["critic_obs_norm_state_dict"] = critic_norm.state_dict()
+        torch.save(saved, path)
         if self.exact_resume:
             torch.save(self._train_state(), train_state_path(path))
 
@@ -246,6 +282,14 @@ class OnPolicyRunner:
 
     def load(self, path, load_optimizer=True):
         loaded = torch.load(path, map_location=self.device, weights_only=False)
+        if ("obs_norm_state_dict" in loaded) != self.empirical_normalization:
+            raise ValueError(f"{path} was saved with empirical_normalization={'obs_norm_state_dict' in loaded}, this runner has "
+                             f"empirical_normalization={self.empirical_normalization}: the policy's inputs would not be what it was trained on "
+                             "(pass --empirical_normalization, or set train_cfg.runner.empirical_normalization, to match the checkpoint)")
+        if self.empirical_normalization:
+            self.obs_normalizer.load_state_dict(loaded["obs_norm_state_dict"])
+            if self.critic_obs_normalizer is not None:
+                self.critic_obs_normalizer.load_state_dict(loaded["critic_obs_norm_state_dict"])
         self.algorithm.actor_critic.load_state_dict(loaded["model_state_dict"])
         self.algorithm.invalidate_graphs()
         if load_optimizer:
@@ -257,6 +301,12 @@ class OnPolicyRunner:
         self.algorithm.actor_critic.eval()
         if device is not None:
             self.algorithm.actor_critic.to(device)
+        if self.empirical_normalization:   # raw observations in, as in training: normalised with the statistics as they are
+            norm, act = self.obs_normalizer, self.algorithm.actor_critic.act_inference
+            norm.eval()
+            if device is not None:
+                norm.to(device)
+            return lambda x: act(norm(x))
         return self.algorithm.actor_critic.act_inference
 
 

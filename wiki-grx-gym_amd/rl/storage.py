@@ -30,6 +30,11 @@ class RolloutStorage:
         self.dones = z(1, dtype=torch.uint8)
         self.num_transitions_per_env, self.num_envs, self.step = T, N, 0
 
+    @property
+    def privileged_observations(self):
+        """rsl_rl's name for the critic's rows (rollout_storage.py:35)"""
+        return self.pri_observations
+
     def add_transitions(self, t):
         if self.step >= self.num_transitions_per_env:
             raise AssertionError("Rollout buffer overflow")

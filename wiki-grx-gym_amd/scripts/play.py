@@ -68,7 +68,8 @@ def play(args, steps=None, log_root="default"):
     out_dir = os.path.join(exp_root, "exported")
     exported = None
     if EXPORT_POLICY:
-        exported = export_policy_as_jit(ppo_runner.algorithm.actor_critic, out_dir)
+        exported = export_policy_as_jit(ppo_runner.algorithm.actor_critic, out_dir,
+                                        normalizer=ppo_runner.obs_normalizer if ppo_runner.empirical_normalization else None)
         print(f"EXPORT_POLICY: Exported policy as jit script to: {exported}")
     os.makedirs(out_dir, exist_ok=True)
 

@@ -60,6 +60,8 @@ def get_args(argv=None):
                    help="PPO's hidden-layer matrix products: fp32 (default) or bf16 operands with fp32 accumulation (HIP only)")
     p.add_argument("--exact_resume", action="store_true", default=False,
                    help="Every checkpoint also saves the whole training state (train_state_<it>.pt); with --resume, continue from it bit for bit")
+    p.add_argument("--empirical_normalization", action="store_true", default=False,
+                   help="Normalise actor and critic observations with their running mean / variance (saved in the checkpoint; play needs the same flag)")
     args = p.parse_args(argv)
     args.sim_device_type, args.compute_device_id = parse_device_str(args.sim_device)
     args.use_gpu_pipeline = args.pipeline.lower() in ("gpu", "cuda")
@@ -94,6 +96,8 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
             cfg_train.algorithm.precision = args.precision
         if getattr(args, "exact_resume", False):   # (likewise: the runner config has no such key otherwise)
             cfg_train.runner.exact_resume = True
+        if getattr(args, "empirical_normalization", False):   # (likewise)
+            cfg_train.runner.empirical_normalization = True
     return env_cfg, cfg_train
 
 
@@ -127,9 +131,13 @@ def get_load_path(root, load_run=-1, checkpoint=-1):
     return os.path.join(load_run, model)
 
 
-def export_policy_as_jit(actor_critic, path):
+def export_policy_as_jit(actor_critic, path, normalizer=None):
+    """`normalizer` (an rl.normalizer.EmpiricalNormalization): the exported module takes RAW observations and normalises them itself"""
     os.makedirs(path, exist_ok=True)
     path = os.path.join(path, "policy_jit.pt")
     model = copy.deepcopy(actor_critic.actor).to("cpu")
+    if normalizer is not None:
+        from ..rl.normalizer import NormalizedPolicy
+        model = NormalizedPolicy(model, copy.deepcopy(normalizer).to("cpu"))
     torch.jit.script(model).save(path)
     return path
