@@ -159,6 +159,17 @@ int grx_obs_norm_apply(int rows, int cols, const float* x, const float* mean, co
 int grx_obs_norm_step(int rows, int cols, const float* x, float* partials, long long* count, float* mean, float* var, float* std, float eps,
                       float* y, void* stream);
 
+/* Observation history (humanoid-gym `frame_stack`, Isaac Lab / rsl_rl 2.x `history_length`; rl/history.py): the policy
+ * sees the last H frames of an observation of width D.  The stacked row of env n is H frames, oldest first, newest last:
+ *   dones[n] == 0:  dst[n] = concat(src[n][D:], obs[n])       (shift by one frame, append the new one)
+ *   dones[n] != 0:  dst[n] = obs[n] repeated H times          (obs[n] is already the first frame of the new episode)
+ * dst [N][H*D] from src [N][H*D] and the new frame obs [N][D]; dones [N] uint8 or NULL; fill_all != 0 or dones == NULL: every row
+ * filled (src is not read and may be NULL).  H == 1: dst = obs.  Out of place: src and dst are two buffers that the caller alternates.
+ * One launch, pure copies (exact), no atomics.  Return 0, or negative with nothing launched for N, D, H < 1, N*H*D >= 2^31, NULL obs
+ * or dst, NULL src when a row may shift, src == dst or overlapping src / dst or obs / dst ranges; negative for a failed launch. */
+int grx_obs_history_push(int N, int D, int H, const float* obs, const unsigned char* dones, int fill_all, const float* src, float* dst,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

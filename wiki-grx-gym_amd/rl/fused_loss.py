@@ -66,6 +66,9 @@ def load_ppo_library():
         lib.grx_obs_norm_apply.argtypes = [C.c_int, C.c_int, fp, fp, fp, C.c_float, fp, C.c_void_p]
         lib.grx_obs_norm_step.restype = C.c_int
         lib.grx_obs_norm_step.argtypes = [C.c_int, C.c_int] + [fp] * 6 + [C.c_float, fp, C.c_void_p]
+        # the observation history (rl/history.py)
+        lib.grx_obs_history_push.restype = C.c_int
+        lib.grx_obs_history_push.argtypes = [C.c_int] * 3 + [fp, fp, C.c_int, fp, fp, C.c_void_p]
         _LIB = lib
     return _LIB
 

@@ -18,8 +18,9 @@ from collections import deque
 import torch
 import torch.distributed as dist
 
+from .history import HistoryPolicy, ObsHistory
 from .modules import ActorCriticMLP
-from .normalizer import EmpiricalNormalization, normalize_step
+from .normalizer import EmpiricalNormalization, NormalizedPolicy, normalize_step
 from .ppo import PPO
 from .storage import RolloutStorage  # noqa: F401
 
@@ -51,11 +52,28 @@ class OnPolicyRunner:
     def __init__(self, env, train_cfg, log_dir=None, device="cpu"):
         self.cfg, self.algorithm_cfg, self.policy_cfg = train_cfg["runner"], train_cfg["algorithm"], train_cfg["policy"]
         self.device, self.env = device, env
-        critic_in = env.num_pri_obs if env.num_pri_obs is not None else env.num_obs
         policy_cls = _POLICIES[self.cfg["policy_class_name"]]
         if dist.is_available() and dist.is_initialized():
             torch.manual_seed(int(train_cfg.get("seed", 1)))      # identical replicas on every rank
-        actor_critic = policy_cls(env.num_obs, critic_in, env.num_actions, **self.policy_cfg).to(device)
+        # observation history: the policy sees the last H frames (the critic the last Hc privileged frames), stacked oldest
+        # first; everything after the stacking -- normaliser, storage, update -- is the same code on a wider tensor.  Not config keys either
+        # (`--obs_history` / `--critic_obs_history` or an assignment to train_cfg.runner sets them); 1 / 1 builds nothing
+        self.obs_history_length = int(self.cfg.get("obs_history_length", 1))
+        self.critic_obs_history_length = int(self.cfg.get("critic_obs_history_length", 1))
+        if self.obs_history_length < 1 or self.critic_obs_history_length < 1:
+            raise ValueError(f"obs_history_length and critic_obs_history_length must be >= 1, got {self.obs_history_length} and "
+                             f"{self.critic_obs_history_length}")
+        if env.num_pri_obs is None and self.critic_obs_history_length != 1:
+            raise ValueError(f"critic_obs_history_length={self.critic_obs_history_length}: this env has no privileged observations, the critic gets "
+                             "the actor's stacked input (set obs_history_length)")
+        self.obs_history = self.critic_obs_history = None
+        if self.obs_history_length > 1:
+            self.obs_history = ObsHistory(env.num_envs, env.num_obs, self.obs_history_length, device)
+        if self.critic_obs_history_length > 1:
+            self.critic_obs_history = ObsHistory(env.num_envs, env.num_pri_obs, self.critic_obs_history_length, device)
+        actor_in = self.obs_history_length * env.num_obs
+        critic_in = self.critic_obs_history_length * env.num_pri_obs if env.num_pri_obs is not None else actor_in
+        actor_critic = policy_cls(actor_in, critic_in, env.num_actions, **self.policy_cfg).to(device)
         self.algorithm = _ALGORITHMS[self.cfg["algorithm_class_name"]](actor_critic=actor_critic, device=device, **self.algorithm_cfg)
         self.alg = self.algorithm
         self.num_steps_per_env, self.save_interval = self.cfg["num_steps_per_env"], self.cfg["save_interval"]
@@ -70,9 +88,9 @@ class OnPolicyRunner:
         self.empirical_normalization = bool(self.cfg.get("empirical_normalization", False))
         self.obs_normalizer = self.critic_obs_normalizer = None
         if self.empirical_normalization:
-            self.obs_normalizer = EmpiricalNormalization(env.num_obs).to(device)
+            self.obs_normalizer = EmpiricalNormalization(actor_in).to(device)   # (history first, then normalisation: the stacked widths)
             if env.num_pri_obs is not None:
-                self.critic_obs_normalizer = EmpiricalNormalization(env.num_pri_obs).to(device)
+                self.critic_obs_normalizer = EmpiricalNormalization(critic_in).to(device)
         self._pending_state = None   # what load_train_state() restored and learn() still has to apply
         self._log_buffers = None     # learn()'s running episode reward / length and the finished episodes' deques
         self._next_iteration = None  # the iteration a save() from inside learn() resumes at
@@ -101,6 +119,9 @@ class OnPolicyRunner:
         pri = env.get_privileged_observations()
         critic_obs = pri if pri is not None else obs
         obs, critic_obs = obs.to(self.device), critic_obs.to(self.device)
+        if self.obs_history is not None or self.critic_obs_history is not None:
+            # a primed history (an earlier learn() call, an exact resume) already holds the current frames: no frame is pushed twice
+            obs, critic_obs = self._stack_history(obs, critic_obs if pri is not None else None, None)
         if self.empirical_normalization:
             # the observations learn() starts from, with the statistics as they are: every observation updates the statistics exactly once,
             # after its env.step (a resumed run's first observations went in before the checkpoint; a fresh run's are x / 1.01)
@@ -137,6 +158,8 @@ class OnPolicyRunner:
                     obs, pri, rewards, dones, infos = env.step(actions)
                     critic_obs = pri if pri is not None else obs
                     obs, critic_obs, rewards, dones = obs.to(self.device), critic_obs.to(self.device), rewards.to(self.device), dones.to(self.device)
+                    if self.obs_history is not None or self.critic_obs_history is not None:
+                        obs, critic_obs = self._stack_history(obs, critic_obs if pri is not None else None, dones)
                     if self.empirical_normalization:
                         obs, critic_obs = self._normalize_step(obs, critic_obs if pri is not None else None)
                     if self.log_dir is not None:
@@ -173,6 +196,22 @@ class OnPolicyRunner:
             self._next_iteration = self.current_learning_iteration
             self.save(os.path.join(self.log_dir, f"model_{self.current_learning_iteration}.pt"))
         self._next_iteration = None
+
+    def _stack_history(self, obs, pri, dones):
+        """one env step's raw frames into the histories: (actor input, critic input).  dones None: learn()'s first frames, which fill a
+        history that is not primed and leave a primed one as it is"""
+        for hist, frame in ((self.obs_history, obs), (self.critic_obs_history, pri)):
+            if hist is None or frame is None:
+                continue
+            if dones is not None:
+                stacked = hist.push(frame, dones)
+            else:
+                stacked = hist.current if hist.primed else hist.fill(frame)
+            if hist is self.obs_history:
+                obs = stacked
+            else:
+                pri = stacked
+        return obs, (pri if pri is not None else obs)
 
     def _normalize_step(self, obs, pri):
         """one env step's observations into the statistics (training mode) and back normalised: (actor input, critic input)"""
@@ -232,6 +271,8 @@ class OnPolicyRunner:
             saved["obs_norm_state_dict"] = self.obs_normalizer.state_dict()
             critic_norm = self.critic_obs_normalizer if self.critic_obs_normalizer is not None else self.obs_normalizer
             saved["critic_obs_norm_state_dict"] = critic_norm.state_dict()
+        if self.obs_history_length > 1 or self.critic_obs_history_length > 1:   # (absent otherwise, as above)
+            saved["obs_history"] = {"actor": self.obs_history_length, "critic": self.critic_obs_history_length}
         torch.save(saved, path)
         if self.exact_resume:
             torch.save(self._train_state(), train_state_path(path))
@@ -240,7 +281,12 @@ class OnPolicyRunner:
         """train_state_<it>.pt: everything besides model_<it>.pt that the run's next iteration depends on"""
         dev = torch.device(self.device)
         cur_rew, cur_len, rewbuffer, lenbuffer = self._log_buffers if self._log_buffers is not None else (None, None, [], [])
+        history = {}
+        if self.obs_history is not None or self.critic_obs_history is not None:   # (no key otherwise: the file is what it was)
+            history = {"obs_history": {"actor": self.obs_history.state_dict() if self.obs_history is not None else None,
+                                       "critic": self.critic_obs_history.state_dict() if self.critic_obs_history is not None else None}}
         return {
+            **history,
             "format": 1,
             "next_iteration": self._next_iteration if self._next_iteration is not None else self.current_learning_iteration,
             "env": self.env.get_state(),
@@ -267,6 +313,14 @@ class OnPolicyRunner:
         if not os.path.exists(path):
             raise FileNotFoundError(f"exact resume: {path} is missing (the run was not saved with exact_resume)")
         state = torch.load(path, map_location="cpu", weights_only=False)
+        saved_hist = state.get("obs_history") or {"actor": None, "critic": None}
+        for which, hist in (("actor", self.obs_history), ("critic", self.critic_obs_history)):
+            if (saved_hist[which] is None) != (hist is None):
+                raise ValueError(f"exact resume: {path} {'holds' if hist is None else 'lacks'} the {which}'s observation history, this runner "
+                                 f"{'has none' if hist is None else 'needs it'} (--obs_history / --critic_obs_history must match the saved run)")
+        for which, hist in (("actor", self.obs_history), ("critic", self.critic_obs_history)):
+            if hist is not None:
+                hist.load_state_dict(saved_hist[which])   # (raises ValueError on other shapes)
         self.env.set_state(state["env"])
         # the parameters exactly as saved: load() keeps the reference's reset of `std` to set_noise_std (actor_critic_mlp.py:116-134)
         saved = torch.load(model_path, map_location=self.device, weights_only=False)["model_state_dict"]
@@ -286,6 +340,12 @@ class OnPolicyRunner:
             raise ValueError(f"{path} was saved with empirical_normalization={'obs_norm_state_dict' in loaded}, this runner has "
                              f"empirical_normalization={self.empirical_normalization}: the policy's inputs would not be what it was trained on "
                              "(pass --empirical_normalization, or set train_cfg.runner.empirical_normalization, to match the checkpoint)")
+        saved_hist = loaded.get("obs_history", {"actor": 1, "critic": 1})   # (a checkpoint without the key: no history)
+        if (saved_hist["actor"], saved_hist["critic"]) != (self.obs_history_length, self.critic_obs_history_length):
+            raise ValueError(f"{path} was saved with --obs_history {saved_hist['actor']} --critic_obs_history {saved_hist['critic']}, this runner has "
+                             f"--obs_history {self.obs_history_length} --critic_obs_history {self.critic_obs_history_length}: the policy's inputs "
+                             "would not be what it was trained on (pass the checkpoint's values, or set train_cfg.runner.obs_history_length / "
+                             "critic_obs_history_length)")
         if self.empirical_normalization:
             self.obs_normalizer.load_state_dict(loaded["obs_norm_state_dict"])
             if self.critic_obs_normalizer is not None:
@@ -301,13 +361,19 @@ class OnPolicyRunner:
         self.algorithm.actor_critic.eval()
         if device is not None:
             self.algorithm.actor_critic.to(device)
+        policy = self.algorithm.actor_critic.act_inference
         if self.empirical_normalization:   # raw observations in, as in training: normalised with the statistics as they are
             norm, act = self.obs_normalizer, self.algorithm.actor_critic.act_inference
             norm.eval()
             if device is not None:
                 norm.to(device)
-            return lambda x: act(norm(x))
-        return self.algorithm.actor_critic.act_inference
+            policy = lambda x: act(norm(x))
+        if self.obs_history_length > 1:   # raw SINGLE frames in: the policy keeps its own history (policy.reset(dones) after every env.step)
+            inner = self.algorithm.actor_critic.actor
+            if self.empirical_normalization:   # (history first, then the statistics as they are now)
+                inner = NormalizedPolicy(inner, self.obs_normalizer)
+            policy = HistoryPolicy(inner, self.env.num_obs, self.obs_history_length).to(device if device is not None else self.device)
+        return policy
 
 
 def train_state_path(model_path):

@@ -69,7 +69,8 @@ def play(args, steps=None, log_root="default"):
     exported = None
     if EXPORT_POLICY:
         exported = export_policy_as_jit(ppo_runner.algorithm.actor_critic, out_dir,
-                                        normalizer=ppo_runner.obs_normalizer if ppo_runner.empirical_normalization else None)
+                                        normalizer=ppo_runner.obs_normalizer if ppo_runner.empirical_normalization else None,
+                                        history=ppo_runner.obs_history_length)
         print(f"EXPORT_POLICY: Exported policy as jit script to: {exported}")
     os.makedirs(out_dir, exist_ok=True)
 
@@ -91,6 +92,8 @@ def play(args, steps=None, log_root="default"):
         for i in range(total):
             actions = policy(obs.detach())
             obs, _, rews, dones, infos = env.step(actions.detach())
+            if hasattr(policy, "reset"):   # (a policy with an observation history refills the rows of the envs that just ended)
+                policy.reset(dones)
 
             if i < stop_state_log:
                 rec = _state_record(env, actions, robot_index, joint_index)

@@ -62,7 +62,13 @@ def get_args(argv=None):
                    help="Every checkpoint also saves the whole training state (train_state_<it>.pt); with --resume, continue from it bit for bit")
     p.add_argument("--empirical_normalization", action="store_true", default=False,
                    help="Normalise actor and critic observations with their running mean / variance (saved in the checkpoint; play needs the same flag)")
+    p.add_argument("--obs_history", type=int, default=1,
+                   help="The policy sees the last N observation frames, oldest first (1: off; saved in the checkpoint; play needs the same value)")
+    p.add_argument("--critic_obs_history", type=int, default=1,
+                   help="The critic sees the last N privileged observation frames (1: off; needs an env with privileged observations)")
     args = p.parse_args(argv)
+    if args.obs_history < 1 or args.critic_obs_history < 1:
+        raise ValueError(f"--obs_history and --critic_obs_history must be >= 1, got {args.obs_history} and {args.critic_obs_history}")
     args.sim_device_type, args.compute_device_id = parse_device_str(args.sim_device)
     args.use_gpu_pipeline = args.pipeline.lower() in ("gpu", "cuda")
     args.use_gpu = args.sim_device_type == "cuda"
@@ -98,6 +104,10 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
             cfg_train.runner.exact_resume = True
         if getattr(args, "empirical_normalization", False):   # (likewise)
             cfg_train.runner.empirical_normalization = True
+        if getattr(args, "obs_history", 1) != 1:   # (likewise)
+            cfg_train.runner.obs_history_length = int(args.obs_history)
+        if getattr(args, "critic_obs_history", 1) != 1:   # (likewise)
+            cfg_train.runner.critic_obs_history_length = int(args.critic_obs_history)
     return env_cfg, cfg_train
 
 
@@ -131,13 +141,21 @@ def get_load_path(root, load_run=-1, checkpoint=-1):
     return os.path.join(load_run, model)
 
 
-def export_policy_as_jit(actor_critic, path, normalizer=None):
-    """`normalizer` (an rl.normalizer.EmpiricalNormalization): the exported module takes RAW observations and normalises them itself"""
+def export_policy_as_jit(actor_critic, path, normalizer=None, history=1):
+    """`normalizer` (an rl.normalizer.EmpiricalNormalization): the exported module takes RAW observations and normalises them itself.
+    `history` > 1 (the runner's obs_history_length): it takes raw SINGLE frames and keeps the last `history` of them itself
+    (rl.history.HistoryPolicy: `reset_memory()` and `reset(dones)` are exported methods)"""
     os.makedirs(path, exist_ok=True)
     path = os.path.join(path, "policy_jit.pt")
     model = copy.deepcopy(actor_critic.actor).to("cpu")
     if normalizer is not None:
         from ..rl.normalizer import NormalizedPolicy
         model = NormalizedPolicy(model, copy.deepcopy(normalizer).to("cpu"))
+    if history > 1:
+        from ..rl.history import HistoryPolicy
+        stacked = actor_critic.actor.model[0].in_features
+        if stacked % history:
+            raise ValueError(f"export_policy_as_jit: the actor takes {stacked} inputs, no multiple of history={history}")
+        model = HistoryPolicy(model, stacked // history, history)
     torch.jit.script(model).save(path)
     return path
