@@ -69,6 +69,7 @@ SENS_K = 10.0
 # Round 6: ONE table per test class, each entry ~2 x the largest ratio any test of that class showed in round 5 (profiles/r05_phys_fracs.jsonl;
 # round 5 used the rough full body's numbers for every test, so a plane test could be out by 1500 x its tolerance and pass):
 #   (heightfield?, full body?) -> {tensor: cap}, "*": every other tensor
+# (what these caps cannot see -- a contact force off by a few newtons -- is pinned one sub-step at a time: tests/substep.py)
 HARD_CAPS = {
     (False, False): {"ROOT_STATES": 180.0, "*": 100.0},                                                             # observed <= 88 / 49
     (False, True): {"DOF_POS": 470.0, "ROOT_STATES": 450.0, "COMMANDS": 200.0, "TORQUES": 160.0, "DOF_VEL": 120.0, "LAST_DOF_VEL": 120.0, "*": 100.0},   # 234 / 220 / 95 / 80 / 60
