@@ -21,6 +21,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
+from tests import robot_zoo
 from tests.helpers import STATE_TENSORS, make_cfg, random_actions
 from wiki_grx_gym_amd.envs import build_config
 
@@ -54,16 +55,20 @@ class Scene:
     name: str
     cls: str                      # band class: "plane" / "raster" (lower limb), "full" (32-DOF body)
     task: str = "GR1T1"
+    model: str = None             # a model of tests/robot_zoo.py instead of a task (the test points model.ASSET_DIR at the zoo: robot_zoo.install)
     ground: str = "plane"         # "plane" / "slope" / "stairs"
     mesh: str = "plane"           # terrain head: "plane" / "heightfield" / "trimesh"
     N: int = 64
     friction: tuple = None        # domain_rand.friction_range override
     scales: tuple = (0.5, 0.5)    # action scale of the first / second half of the run
-    script: str = None            # "legs": the leg-crossing poses of test_self_collision_matches_the_oracle, in flight
+    script: str = None            # "legs": the leg-crossing poses of test_self_collision_matches_the_oracle, in flight; zoo models: "drop" (from
+                                  # 0.1-0.3 m onto the ground, joints near the default pose), "spread" (in flight, joints over 90 % of their ranges)
     base: bool = False            # legged_gym's base reward terms on (the *_base kernel entries)
     seed: int = 1
     episode_s: float = None       # env.episode_length_s: 0.5 s = 250 sub-steps, so that every env also times out within the run
     slip_dominates: bool = False  # low friction: the anchors of most rows in foot contact are dragged
+    swap_pairs: bool = False      # every second self-collision sphere pair handed over as (b, a): the higher body first, which model.fill_model never emits
+                                  # (build_gen_tables' `ba > bb` swap; the pairs of one link pair then arrive in both orders)
     reach: tuple = ()             # regime counters this scene is meant to reach (>= MIN_REGIME env-sub-steps)
 
     @property
@@ -98,6 +103,25 @@ SCENES = {s.name: s for s in (
 )}
 
 
+# The zoo (tests/robot_zoo.py), one band class per model (stairs: one of its own); python -m tests.robot_zoo measures ZOO_BAND.
+_DROP = _CONTACT + ("reset", "joint_limit")   # (reset: termination contacts and the 0.3 s time-outs)
+ZOO_SCENES = {s.name: s for s in (
+    [Scene(f"{m}_drop", m, model=m, script="drop", scales=(1.0, 0.5), seed=1, episode_s=0.3,
+           reach=_CONTACT + ("reset",) if m.startswith("wide") else _DROP)   # (wide*: the spokes carry the base, their joints stay inside the limits)
+     for m in robot_zoo.MODELS]
+    + [Scene(f"{m}_spread", m, model=m, script="spread", scales=(1.0, 1.0), seed=5, reach=("self_collision",)) for m in robot_zoo.WITH_PAIRS]
+    + [Scene("pairs65_swapped", "pairs65", model="pairs65", script="spread", scales=(1.0, 1.0), seed=6, swap_pairs=True, reach=("self_collision",))]
+    + [Scene("skew_stairs", "skew_stairs", model="skew", ground="stairs", mesh="trimesh", friction=(0.05, 0.05), seed=2, reach=_CONTACT + ("face_contact",))])}
+
+
+def scene_of(name):
+    return SCENES[name] if name in SCENES else ZOO_SCENES[name]
+
+
+def band_of(scene):
+    return SUBSTEP_BAND[scene.cls] if scene.cls in SUBSTEP_BAND else robot_zoo.ZOO_BAND[scene.cls]
+
+
 def substep_cfg(task="GR1T1", terrain="plane", **kw):
     """tests.helpers.make_cfg with ONE physics sub-step per step."""
     cfg = make_cfg(task=task, terrain=terrain, **kw)
@@ -121,7 +145,7 @@ def one_tile_scene(kind):
 
 def scene_cfg(scene):
     """(cfg, terrain or None) of a scene."""
-    cfg = substep_cfg(scene.task, scene.mesh, curriculum=False, dr=True, push=False)
+    cfg = substep_cfg(robot_zoo.cfg_class(scene.model) if scene.model else scene.task, scene.mesh, curriculum=False, dr=True, push=False)
     ter = None
     if scene.ground != "plane":
         ter = one_tile_scene(scene.ground)
@@ -145,6 +169,9 @@ def scene_cfg(scene):
 def build_struct(scene):
     cfg, ter = scene_cfg(scene)
     c, keep, meta = build_config.build(cfg, cfg.sim.dt, scene.N, 0, None, scene.seed, ter)
+    if scene.swap_pairs:
+        for k in range(0, c.model.num_pairs, 2):
+            c.model.pair_a[k], c.model.pair_b[k] = c.model.pair_b[k], c.model.pair_a[k]
     return cfg, c, keep, meta
 
 
@@ -160,16 +187,16 @@ def make_hip(scene):
     return HipSim(c, "cuda:0", keep)
 
 
-def _place_on_tile(ora, q0, gen):
-    """tests/test_hip_parity.stairs_tile_scene's placement: spread over the tile, 0.93 m above the ground under them, moving at 0.8-1.2 m/s
-    in a random direction."""
+def _place_on_tile(ora, q0, gen, height=0.93):
+    """tests/test_hip_parity.stairs_tile_scene's placement: spread over the tile, 0.93 m (the GR1's standing height; `height`) above the ground
+    under them, moving at 0.8-1.2 m/s in a random direction."""
     N = ora.num_envs
     root = torch.zeros(N, 13)
     root[:, 6] = 1.0
     xy = 1.0 + 5.9 * torch.rand(N, 2, generator=gen)
     root[:, 0:2] = xy
     for i in range(N):
-        root[i, 2] = float(ora.terrain(float(xy[i, 0]), float(xy[i, 1]))[0]) + 0.93
+        root[i, 2] = float(ora.terrain(float(xy[i, 0]), float(xy[i, 1]))[0]) + height
     ang = 6.2832 * torch.rand(N, generator=gen)
     speed = 0.8 + 0.4 * torch.rand(N, generator=gen)
     root[:, 7] = speed * torch.cos(ang)
@@ -188,6 +215,34 @@ def _place_legs_crossed(ora, gen):
     q = torch.tensor([[-0.35, 0.0, -0.3, 0.6, -0.3, 0.35, 0.0, -0.3, 0.6, -0.3]]).repeat(N, 1)
     q += (torch.rand(N, 10, generator=gen) - 0.5) * torch.tensor([0.5, 0.8, 0.8, 0.6, 0.4] * 2)
     qd = torch.randn(N, 10, generator=gen) * 2.0
+    ora.set_state(root.contiguous(), q.contiguous(), qd.contiguous())
+
+
+def _place_drop(ora, rm, q0, gen):
+    """Zoo models: the base tilted by up to ~0.2 rad, the joints within 0.2 rad of the default pose (inside their limits), the lowest collision
+    sphere 0.1-0.3 m above the plane, at rest."""
+    from tests.kinematics_ref import BodyKinematics
+    N = ora.num_envs
+    lo, hi = torch.tensor(rm.dof_lower, dtype=torch.float32), torch.tensor(rm.dof_upper, dtype=torch.float32)
+    q = torch.minimum(torch.maximum(q0 + 0.4 * (torch.rand(N, rm.num_dofs, generator=gen) - 0.5), lo), hi)
+    root = torch.zeros(N, 13)
+    quat = torch.cat([0.1 * torch.randn(N, 3, generator=gen), torch.ones(N, 1)], 1)
+    root[:, 3:7] = quat / quat.norm(dim=1, keepdim=True)
+    root[:, 2] = 0.1 + 0.2 * torch.rand(N, generator=gen) - robot_zoo.lowest_point(rm, BodyKinematics(rm, "cpu"), root, q)
+    ora.set_state(root.contiguous(), q.contiguous(), torch.zeros_like(q))
+
+
+def _place_spread(ora, rm, gen):
+    """Zoo models in flight (3 m up), every joint anywhere in 90 % of its range and moving: the poses in which the model's self-collision
+    pairs carry load."""
+    N = ora.num_envs
+    lo, hi = torch.tensor(rm.dof_lower, dtype=torch.float32), torch.tensor(rm.dof_upper, dtype=torch.float32)
+    root = torch.zeros(N, 13)
+    root[:, 2] = 3.0
+    root[:, 6] = 1.0
+    root[:, 7:13] = torch.randn(N, 6, generator=gen) * 0.3
+    q = (lo + hi) / 2 + (2 * torch.rand(N, rm.num_dofs, generator=gen) - 1) * 0.9 * (hi - lo) / 2
+    qd = torch.randn(N, rm.num_dofs, generator=gen)
     ora.set_state(root.contiguous(), q.contiguous(), qd.contiguous())
 
 
@@ -223,7 +278,11 @@ def run_oracle(scene, steps=SUBSTEPS):
     pre, ref, acts, delays = [], [], [], []
     for t in range(steps):
         if scene.ground != "plane" and t % REPLACE_EVERY == 0:
-            _place_on_tile(ora, q0, pgen)
+            _place_on_tile(ora, q0, pgen, *([robot_zoo.rest_height(scene.model) + 0.1] if scene.model else []))
+        if scene.script == "drop" and t % REPLACE_EVERY == 0:
+            _place_drop(ora, meta["model"], q0, pgen)
+        if scene.script == "spread" and t % LEGS_REPLACE_EVERY == 0:
+            _place_spread(ora, meta["model"], pgen)
         if scene.script == "legs" and t % LEGS_REPLACE_EVERY == 0:
             _place_legs_crossed(ora, pgen)
         pre.append(_snapshot(ora, STATE_TENSORS))
@@ -254,7 +313,7 @@ def oracle_trajectory(name):
     other in their parametrisation."""
     if name not in _cache:
         _cache.clear()
-        _cache[name] = run_oracle(SCENES[name])
+        _cache[name] = run_oracle(scene_of(name))
     return _cache[name]
 
 
@@ -346,7 +405,7 @@ def check(traj, got, label, log=None):
     """The sub-step conditions on `got` (a replay of traj): every row in band and every discrete output identical, but for the scene's
     caps.  Returns the report (also appended to `log`, a jsonl path, with every counted row)."""
     scene = traj.scene
-    band = SUBSTEP_BAND[scene.cls]
+    band = band_of(scene)
     cmp = compare(traj, got)
     out = torch.zeros_like(cmp["flags"])
     rows = []
@@ -392,11 +451,28 @@ def band_from(per_scene):
     """SUBSTEP_BAND of measured maxima {scene: {tensor: max}}: SENS_K x the largest of the class, rounded up to two digits."""
     band = {}
     for name, mx in per_scene.items():
-        b = band.setdefault(SCENES[name].cls, {})
-        for n in SCENES[name].banded:
+        b = band.setdefault(scene_of(name).cls, {})
+        for n in scene_of(name).banded:
             b[n] = max(b.get(n, 0.0), SENS_K * mx[n])
     up = lambda v: float(np.format_float_scientific(v * (1 + 1e-9) + 0.5 * 10.0 ** (np.floor(np.log10(v)) - 1), precision=1)) if v > 0 else 0.0
     return {c: {n: up(v) for n, v in b.items()} for c, b in band.items()}
+
+
+def write_zoo_bands():
+    """python -m tests.robot_zoo: measure the zoo's bands inside robot_zoo.installed() (needs robot_zoo.ZOO_BAND only to exist), write profiles/zoo_bands.json, print ZOO_BAND."""
+    per_scene, counters, rows = {}, {}, {}
+    for name in ZOO_SCENES:
+        per_scene[name], cmp, traj = measure_fp32(name)
+        counters[name] = regime_counters(traj)
+        rows[name] = {"flag_rows": int(cmp["flags"].sum()), "threshold_rows": int(cmp["thresholds"].sum())}
+        print(name, counters[name], rows[name], flush=True)
+    band = band_from(per_scene)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "profiles", "zoo_bands.json"), "w") as f:
+        json.dump({"what": "largest |fp32 oracle - fp64 oracle| per zoo scene (tests/substep.ZOO_SCENES over tests/robot_zoo.py's models) and tensor: one "
+                           "sub-step from identical fp32 state, 600 sub-steps, 64 envs; band = SENS_K x the largest of a class",
+                   "sens_k": SENS_K, "maxima": per_scene, "regime_counters": counters, "fp32_rows": rows, "band": band}, f, indent=1)
+    print("ZOO_BAND = {\n" + "\n".join(f"    {json.dumps(c)}: {json.dumps(b)}," for c, b in band.items()) + "\n}")
 
 
 if __name__ == "__main__":      # python -m tests.substep: measure the bands again, write profiles/substep_bands.json, print SUBSTEP_BAND

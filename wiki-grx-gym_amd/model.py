@@ -68,8 +68,8 @@ class RobotModel:
     """Lumped model + named frames.  Attributes mirror what the reference reads from the asset:
     ``body_names`` (37), ``dof_names``, per-DOF limits, plus the merged dynamics tables."""
 
-    def __init__(self, key):
-        with open(os.path.join(ASSET_DIR, key + ".model.json")) as f:
+    def __init__(self, key, asset_dir=None):
+        with open(os.path.join(asset_dir or ASSET_DIR, key + ".model.json")) as f:
             raw = json.load(f)
         self.key = key
         self.raw = raw
@@ -79,6 +79,8 @@ class RobotModel:
         self.num_links = len(links)
         self.num_dofs = len(self.dof_names)
         nb = 1 + self.num_dofs
+        if self.num_dofs > _capi.MAX_DOFS:
+            raise ValueError(f"too many DOFs ({self.num_dofs} > GRX_MAX_DOFS = {_capi.MAX_DOFS})")
         if nb > _capi.MAX_BODIES:
             raise ValueError("too many moving bodies")
         self.num_bodies = nb
