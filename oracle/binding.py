@@ -37,6 +37,7 @@ def load(precision="f32"):
         dp = C.POINTER(C.c_double)
         lib.gro_debug_post_physics.argtypes = [H, C.c_int, C.POINTER(PipelineState), C.c_int, C.POINTER(_capi.StepArgs)]
         lib.gro_debug_reward_terms.argtypes = [H, C.c_int, C.POINTER(C.c_float)]
+        lib.gro_debug_episode_terms.argtypes = [H, dp, dp]
         lib.gro_debug_torques.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.gro_debug_forward_dynamics.argtypes = [H, C.c_int, dp, C.c_int, dp, dp]
         lib.gro_debug_inverse_dynamics.argtypes = [H, C.c_int, dp, dp, dp, dp]
@@ -157,6 +158,15 @@ class OracleSim(SimHandle):
         out = (C.c_float * _capi.NUM_REWARD_TERMS)()
         self._check(self.lib.gro_debug_reward_terms(self._h, env, out), "reward_terms")
         return np.array(out[:], dtype=np.float32)
+
+    def episode_terms(self):
+        """(episode sums, the last step's scaled reward terms), float64 (NUM_REWARD_TERMS, N) each, at the oracle's own precision: the
+        published EPISODE_SUMS / REWARD_TERMS are their float32 casts."""
+        n = _capi.NUM_REWARD_TERMS * self.num_envs
+        sums, sp = self._d(np.zeros(n))
+        terms, tp = self._d(np.zeros(n))
+        self._check(self.lib.gro_debug_episode_terms(self._h, sp, tp), "episode_terms")
+        return sums.reshape(_capi.NUM_REWARD_TERMS, -1), terms.reshape(_capi.NUM_REWARD_TERMS, -1)
 
     def torques(self, actions):
         actions = np.ascontiguousarray(actions, dtype=np.float32)

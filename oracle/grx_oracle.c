@@ -2017,6 +2017,18 @@ int gro_debug_reward_terms(grx_handle s, int le, float* out) {
     return GRX_OK;
 }
 
+/* the running episode sums and the last step's scaled reward terms of every env, [NT][N] each, at the oracle's own precision (the published
+   GRX_T_EPISODE_SUMS / GRX_T_REWARD_TERMS are their float casts): tests/stats_ref.py restates the episode statistics from them */
+int gro_debug_episode_terms(grx_handle s, double* sums, double* terms) {
+    if (!s || !sums || !terms) return fail(GRX_ERR_INVALID_ARGUMENT, "gro_debug_episode_terms: null argument");
+    for (int i = 0; i < s->N; ++i)
+        for (int t = 0; t < NT; ++t) {
+            sums[(size_t)t * s->N + i] = (double)s->env[i].episode_sums[t];
+            terms[(size_t)t * s->N + i] = (double)s->env[i].reward_terms[t];
+        }
+    return GRX_OK;
+}
+
 /* torques for (actions) from the current state, no physics: _compute_torques + clip_actions */
 int gro_debug_torques(grx_handle s, const float* actions, float* clipped, float* torques) {
     const grx_config* c = &s->cfg;
