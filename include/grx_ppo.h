@@ -170,6 +170,26 @@ int grx_obs_norm_step(int rows, int cols, const float* x, float* partials, long 
 int grx_obs_history_push(int N, int D, int H, const float* obs, const unsigned char* dones, int fill_all, const float* src, float* dst,
                          void* stream);
 
+/* Teacher-student policy distillation (rsl_rl 2.x `Distillation` / `StudentTeacher`; rl/distillation.py).
+ *   grx_distill_loss: the behaviour loss of one minibatch and its gradient.  student_mu, teacher_mu [batch][A] contiguous; d = student -
+ *                     teacher; huber == 0: e = d^2 (torch mse_loss), huber != 0: e = |d| <= 1 ? d^2 / 2 : |d| - 1 / 2 (torch huber_loss,
+ *                     delta 1); out[0] = the mean of e over all batch * A elements, d_mu [batch][A] = d out[0] / d student_mu =
+ *                     d * fl(2 / n), or clamp(d, -1, 1) * fl(1 / n).  Two launches: per-block partial sums (double), then one block that
+ *                     adds them in block order; no atomics, the order of every sum is a function of batch * A alone.  A NaN in either
+ *                     input gives a NaN out[0].  `partials`: 8-byte aligned scratch of grx_distill_loss_partials_size(batch, A) floats
+ *                     (0: invalid sizes).  Any batch >= 1, A >= 1 with batch * A < 2^31.
+ *   grx_distill_store: one rollout step in ONE launch: st_obs (N, D) = obs, st_labels (N, A) = labels, st_dones (N) uint8 = dones != 0,
+ *                     each the contiguous storage row of this step, copied by dword; logging (all four may be NULL, `rewards` (N) may
+ *                     then be NULL too): cur_rew += rewards, cur_len += 1, done_rew / done_len = the totals where done, cur_* zeroed
+ *                     there -- grx_ppo_store_transition's arithmetic.
+ * Return 0, or negative for invalid sizes / NULL pointers (nothing is launched, nothing written) / a failed launch. */
+int grx_distill_loss_partials_size(int batch, int A);
+int grx_distill_loss(int batch, int A, const float* student_mu, const float* teacher_mu, int huber, float* out, float* d_mu, float* partials,
+                     void* stream);
+int grx_distill_store(int N, int D, int A, const float* obs, const float* labels, const float* rewards, const unsigned char* dones,
+                      float* st_obs, float* st_labels, unsigned char* st_dones,
+                      float* cur_rew, float* cur_len, float* done_rew, float* done_len, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

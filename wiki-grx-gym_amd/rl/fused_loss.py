@@ -69,6 +69,13 @@ def load_ppo_library():
         # the observation history (rl/history.py)
         lib.grx_obs_history_push.restype = C.c_int
         lib.grx_obs_history_push.argtypes = [C.c_int] * 3 + [fp, fp, C.c_int, fp, fp, C.c_void_p]
+        # policy distillation (rl/distillation.py)
+        lib.grx_distill_loss_partials_size.restype = C.c_int
+        lib.grx_distill_loss_partials_size.argtypes = [C.c_int, C.c_int]
+        lib.grx_distill_loss.restype = C.c_int
+        lib.grx_distill_loss.argtypes = [C.c_int, C.c_int, fp, fp, C.c_int, fp, fp, fp, C.c_void_p]
+        lib.grx_distill_store.restype = C.c_int
+        lib.grx_distill_store.argtypes = [C.c_int] * 3 + [fp] * 11 + [C.c_void_p]
         _LIB = lib
     return _LIB
 

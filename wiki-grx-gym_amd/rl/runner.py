@@ -18,6 +18,7 @@ from collections import deque
 import torch
 import torch.distributed as dist
 
+from .distillation import Distillation, StudentTeacher, read_teacher
 from .history import HistoryPolicy, ObsHistory
 from .modules import ActorCriticMLP
 from .normalizer import EmpiricalNormalization, NormalizedPolicy, normalize_step
@@ -25,7 +26,7 @@ from .ppo import PPO
 from .storage import RolloutStorage  # noqa: F401
 
 _POLICIES = {"ActorCriticMLP": ActorCriticMLP, "ActorCritic": ActorCriticMLP}
-_ALGORITHMS = {"PPO": PPO}
+_ALGORITHMS = {"PPO": PPO, "Distillation": Distillation}
 
 
 class _ScalarLog:
@@ -66,6 +67,17 @@ class OnPolicyRunner:
         if env.num_pri_obs is None and self.critic_obs_history_length != 1:
             raise ValueError(f"critic_obs_history_length={self.critic_obs_history_length}: this env has no privileged observations, the critic gets "
                              "the actor's stacked input (set obs_history_length)")
+        # a privileged actor and distillation.  privileged_actor: the actor reads the tensor the critic gets (a teacher that
+        # can be trained).  distill_from: a student on the actor stream is regressed on the frozen actor of that checkpoint, whose stream travels
+        # in the critic's slot.  Not config keys either (`--privileged_actor` / `--distill_from` or an assignment to train_cfg.runner sets them)
+        self.privileged_actor = bool(self.cfg.get("privileged_actor", False))
+        self.distill_from = self.cfg.get("distill_from") or None
+        self.distillation = None   # the "distillation" entry of a checkpoint of this run
+        self._alt_inputs = None    # what builds (actor input, critic-slot input) from one step's raw frames in these two modes
+        if self.privileged_actor:
+            self._check_privileged_actor(env)
+        if self.distill_from is not None:
+            teacher = self._check_distillation(env, device)
         self.obs_history = self.critic_obs_history = None
         if self.obs_history_length > 1:
             self.obs_history = ObsHistory(env.num_envs, env.num_obs, self.obs_history_length, device)
@@ -73,8 +85,29 @@ class OnPolicyRunner:
             self.critic_obs_history = ObsHistory(env.num_envs, env.num_pri_obs, self.critic_obs_history_length, device)
         actor_in = self.obs_history_length * env.num_obs
         critic_in = self.critic_obs_history_length * env.num_pri_obs if env.num_pri_obs is not None else actor_in
-        actor_critic = policy_cls(actor_in, critic_in, env.num_actions, **self.policy_cfg).to(device)
-        self.algorithm = _ALGORITHMS[self.cfg["algorithm_class_name"]](actor_critic=actor_critic, device=device, **self.algorithm_cfg)
+        if self.privileged_actor:
+            actor_in = critic_in
+        if self.distill_from is not None:
+            self.teacher_history = ObsHistory(env.num_envs, teacher["frame"], teacher["history"], device) if teacher["history"] > 1 else None
+            self.teacher_obs_normalizer = None
+            if teacher["norm"] is not None:   # the checkpoint's statistics of that stream, frozen: applied, never updated
+                self.teacher_obs_normalizer = EmpiricalNormalization(teacher["width"]).to(device)
+                self.teacher_obs_normalizer.load_state_dict(teacher["norm"])
+                self.teacher_obs_normalizer.eval()
+            actor_critic = StudentTeacher(actor_in, teacher["width"], env.num_actions, actor_hidden_dims=self.policy_cfg["actor_hidden_dims"],
+                                          teacher_hidden_dims=teacher["hidden"], activation=self.policy_cfg.get("activation", "elu"),
+                                          noise_std=float(self.cfg.get("distill_noise_std", 0.1))).to(device)
+            actor_critic.load_teacher(teacher["state"])
+            self.algorithm = _ALGORITHMS["Distillation"](actor_critic=actor_critic, device=device, loss_type=self.cfg.get("distill_loss", "mse"),
+                                                         **self.algorithm_cfg)
+            self.distillation = {"teacher_stream": teacher["stream"], "teacher_history": teacher["history"], "teacher_width": teacher["width"],
+                                 "loss": self.algorithm.loss_type}
+            self._alt_inputs = self._distill_inputs
+        else:
+            actor_critic = policy_cls(actor_in, critic_in, env.num_actions, **self.policy_cfg).to(device)
+            self.algorithm = _ALGORITHMS[self.cfg["algorithm_class_name"]](actor_critic=actor_critic, device=device, **self.algorithm_cfg)
+            if self.privileged_actor:
+                self._alt_inputs = self._privileged_inputs
         self.alg = self.algorithm
         self.num_steps_per_env, self.save_interval = self.cfg["num_steps_per_env"], self.cfg["save_interval"]
         # exact resume: every save() also writes train_state_<it>.pt, the whole training state; not a config key
@@ -82,14 +115,17 @@ class OnPolicyRunner:
         self.exact_resume = bool(self.cfg.get("exact_resume", False))
         if self.exact_resume and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise NotImplementedError("exact_resume: one process only (with more ranks every rank holds its own env shard)")
+        if self.exact_resume and self.distill_from is not None:
+            raise NotImplementedError("exact_resume: not available for a distillation run (--distill_from)")
         # empirical observation normalisation: running mean / variance of the actor's and -- when the env has privileged
         # observations -- the critic's inputs; what the policy acts on, what the storage keeps and what compute_returns gets are the
         # normalised tensors.  Not a config key either (`--empirical_normalization` or an assignment to train_cfg.runner sets it)
         self.empirical_normalization = bool(self.cfg.get("empirical_normalization", False))
         self.obs_normalizer = self.critic_obs_normalizer = None
         if self.empirical_normalization:
-            self.obs_normalizer = EmpiricalNormalization(actor_in).to(device)   # (history first, then normalisation: the stacked widths)
-            if env.num_pri_obs is not None:
+            if not self.privileged_actor:   # (a privileged actor reads the critic's normalised tensor: no actor-side statistics)
+                self.obs_normalizer = EmpiricalNormalization(actor_in).to(device)   # (history first, then normalisation: the stacked widths)
+            if env.num_pri_obs is not None and self.distill_from is None:   # (a distillation run has no critic)
                 self.critic_obs_normalizer = EmpiricalNormalization(critic_in).to(device)
         self._pending_state = None   # what load_train_state() restored and learn() still has to apply
         self._log_buffers = None     # learn()'s running episode reward / length and the finished episodes' deques
@@ -119,10 +155,12 @@ class OnPolicyRunner:
         pri = env.get_privileged_observations()
         critic_obs = pri if pri is not None else obs
         obs, critic_obs = obs.to(self.device), critic_obs.to(self.device)
-        if self.obs_history is not None or self.critic_obs_history is not None:
+        if self._alt_inputs is not None:   # (privileged actor, distillation: history and normalisation of both inputs in there)
+            obs, critic_obs = self._alt_inputs(obs, critic_obs if pri is not None else None, None)
+        elif self.obs_history is not None or self.critic_obs_history is not None:
             # a primed history (an earlier learn() call, an exact resume) already holds the current frames: no frame is pushed twice
             obs, critic_obs = self._stack_history(obs, critic_obs if pri is not None else None, None)
-        if self.empirical_normalization:
+        if self.empirical_normalization and self._alt_inputs is None:
             # the observations learn() starts from, with the statistics as they are: every observation updates the statistics exactly once,
             # after its env.step (a resumed run's first observations went in before the checkpoint; a fresh run's are x / 1.01)
             self.obs_normalizer.train()
@@ -158,9 +196,11 @@ class OnPolicyRunner:
                     obs, pri, rewards, dones, infos = env.step(actions)
                     critic_obs = pri if pri is not None else obs
                     obs, critic_obs, rewards, dones = obs.to(self.device), critic_obs.to(self.device), rewards.to(self.device), dones.to(self.device)
-                    if self.obs_history is not None or self.critic_obs_history is not None:
+                    if self._alt_inputs is not None:
+                        obs, critic_obs = self._alt_inputs(obs, critic_obs if pri is not None else None, dones)
+                    elif self.obs_history is not None or self.critic_obs_history is not None:
                         obs, critic_obs = self._stack_history(obs, critic_obs if pri is not None else None, dones)
-                    if self.empirical_normalization:
+                    if self.empirical_normalization and self._alt_inputs is None:
                         obs, critic_obs = self._normalize_step(obs, critic_obs if pri is not None else None)
                     if self.log_dir is not None:
                         if "episode" in infos:
@@ -179,7 +219,10 @@ class OnPolicyRunner:
                 collection_time = time.time() - start
                 start = time.time()
                 alg.compute_returns(critic_obs)
-            mean_value_loss, mean_surrogate_loss = alg.update()
+            if self.distillation is not None:
+                mean_behavior_loss = alg.update()
+            else:
+                mean_value_loss, mean_surrogate_loss = alg.update()
             alg.clear_storage()
             if self.sync_timers:
                 torch.cuda.synchronize()
@@ -213,6 +256,66 @@ class OnPolicyRunner:
                 pri = stacked
         return obs, (pri if pri is not None else obs)
 
+    @staticmethod
+    def _stacked(hist, frame, dones):
+        """one history's rows after this frame (dones None: learn()'s first frames, as in _stack_history)"""
+        if dones is not None:
+            return hist.push(frame, dones)
+        return hist.current if hist.primed else hist.fill(frame)
+
+    def _privileged_inputs(self, obs, pri, dones):
+        """--privileged_actor: the critic's tensor -- privileged frames, stacked, normalised with the critic's statistics -- is the actor's too"""
+        x = pri
+        if self.critic_obs_history is not None:
+            x = self._stacked(self.critic_obs_history, x, dones)
+        if self.empirical_normalization:
+            norm = self.critic_obs_normalizer
+            if dones is None:   # learn()'s first observations: the statistics as they are
+                norm.train()
+                x = norm.normalize(x)
+            else:
+                x, = normalize_step([norm], [x])
+        return x, x
+
+    def _distill_inputs(self, obs, pri, dones):
+        """--distill_from: (the student's input, the teacher's input).  The student's is the actor stream as ever; the teacher's its own
+        stream's raw frames, stacked by the checkpoint's history length and normalised with the checkpoint's frozen statistics"""
+        x = pri if self.distillation["teacher_stream"] == "privileged" else obs   # (the raw frames, before the student's stacking)
+        if self.teacher_history is not None:
+            x = self._stacked(self.teacher_history, x, dones)
+        if self.teacher_obs_normalizer is not None:
+            x = self.teacher_obs_normalizer.normalize(x)
+        if self.obs_history is not None:
+            obs = self._stacked(self.obs_history, obs, dones)
+        if self.empirical_normalization:
+            if dones is None:
+                self.obs_normalizer.train()
+                obs = self.obs_normalizer.normalize(obs)
+            else:
+                obs, = normalize_step([self.obs_normalizer], [obs])
+        return obs, x
+
+    def _check_privileged_actor(self, env):
+        if env.num_pri_obs is None:
+            raise ValueError("privileged_actor: this env has no privileged observations for the actor to read")
+        if self.obs_history_length != 1:
+            raise ValueError(f"privileged_actor with obs_history_length={self.obs_history_length}: the actor reads the critic's tensor, whose "
+                             "history is set with --critic_obs_history (train_cfg.runner.critic_obs_history_length)")
+        if self.distill_from is not None:
+            raise ValueError("privileged_actor and distill_from exclude each other: the student reads the actor's observations")
+
+    def _check_distillation(self, env, device):
+        """the refusals of a distillation run; returns what the checkpoint at distill_from says about its actor (distillation.read_teacher)"""
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("distill_from: one process only")
+        if self.algorithm_cfg.get("precision", "fp32") != "fp32":
+            raise ValueError(f"distill_from: precision={self.algorithm_cfg['precision']!r} is not available, the student trains in fp32")
+        if self.critic_obs_history_length != 1:
+            raise ValueError(f"distill_from with critic_obs_history_length={self.critic_obs_history_length}: a distillation run has no critic "
+                             "(the teacher's history length comes from its checkpoint)")
+        loaded = torch.load(self.distill_from, map_location=device, weights_only=False)
+        return read_teacher(loaded, self.distill_from, env.num_obs, env.num_pri_obs, env.num_actions)
+
     def _normalize_step(self, obs, pri):
         """one env step's observations into the statistics (training mode) and back normalised: (actor input, critic input)"""
         if pri is not None and self.critic_obs_normalizer is not None:
@@ -236,10 +339,14 @@ class OnPolicyRunner:
                 ep_string += f"{f'Mean episode {key}:':>{pad}} {value:.4f}\n"
         fps = int(self.num_steps_per_env * self.env.num_envs * self.world / iteration_time)
         alg = self.algorithm
-        w.add_scalar("Loss/value_function", locs["mean_value_loss"], it)
-        w.add_scalar("Loss/surrogate", locs["mean_surrogate_loss"], it)
-        w.add_scalar("Loss/learning_rate", alg.learning_rate, it)
-        w.add_scalar("Loss/kl", alg.mean_kl, it)
+        if self.distillation is not None:
+            w.add_scalar("Loss/behavior", locs["mean_behavior_loss"], it)
+            w.add_scalar("Loss/learning_rate", alg.learning_rate, it)
+        else:
+            w.add_scalar("Loss/value_function", locs["mean_value_loss"], it)
+            w.add_scalar("Loss/surrogate", locs["mean_surrogate_loss"], it)
+            w.add_scalar("Loss/learning_rate", alg.learning_rate, it)
+            w.add_scalar("Loss/kl", alg.mean_kl, it)
         w.add_scalar("Perf/total_fps", fps, it)
         w.add_scalar("Perf/collection time", locs["collection_time"], it)
         w.add_scalar("Perf/learning_time", locs["learn_time"], it)
@@ -256,7 +363,10 @@ class OnPolicyRunner:
         head = f" Learning iteration {it}/{self.current_learning_iteration + locs['num_learning_iterations']} "
         out = f"{'#' * width}\n{head.center(width, ' ')}\n\n"
         out += f"{'Computation:':>{pad}} {fps:.0f} steps/s (collection: {locs['collection_time']:.3f}s, learning {locs['learn_time']:.3f}s)\n"
-        out += f"{'Value function loss:':>{pad}} {locs['mean_value_loss']:.4f}\n{'Surrogate loss:':>{pad}} {locs['mean_surrogate_loss']:.4f}\n"
+        if self.distillation is not None:
+            out += f"{'Behavior loss:':>{pad}} {locs['mean_behavior_loss']:.6f}\n"
+        else:
+            out += f"{'Value function loss:':>{pad}} {locs['mean_value_loss']:.4f}\n{'Surrogate loss:':>{pad}} {locs['mean_surrogate_loss']:.4f}\n"
         out += f"{'Mean action noise std:':>{pad}} {stds.mean().item():.2f}\n"
         if len(locs["rewbuffer"]) > 0:
             out += f"{'Mean reward:':>{pad}} {statistics.mean(locs['rewbuffer']):.2f}\n{'Mean episode length:':>{pad}} {statistics.mean(locs['lenbuffer']):.2f}\n"
@@ -268,11 +378,16 @@ class OnPolicyRunner:
                  "optimizer_state_dict": self.algorithm.optimizer.state_dict(),
                  "iter": self.current_learning_iteration, "infos": infos}
         if self.empirical_normalization:   # (rsl_rl 2.x's keys; absent otherwise: the checkpoint keeps exactly the reference's keys)
-            saved["obs_norm_state_dict"] = self.obs_normalizer.state_dict()
+            actor_norm = self.obs_normalizer if self.obs_normalizer is not None else self.critic_obs_normalizer   # (privileged actor: the critic's)
+            saved["obs_norm_state_dict"] = actor_norm.state_dict()
             critic_norm = self.critic_obs_normalizer if self.critic_obs_normalizer is not None else self.obs_normalizer
             saved["critic_obs_norm_state_dict"] = critic_norm.state_dict()
-        if self.obs_history_length > 1 or self.critic_obs_history_length > 1:   # (absent otherwise, as above)
+        if self.obs_history_length > 1 or self.critic_obs_history_length > 1 or self.distillation is not None:   # (absent otherwise, as above)
             saved["obs_history"] = {"actor": self.obs_history_length, "critic": self.critic_obs_history_length}
+        if self.privileged_actor:   # (absent otherwise)
+            saved["privileged_actor"] = True
+        if self.distillation is not None:   # (likewise)
+            saved["distillation"] = dict(self.distillation)
         torch.save(saved, path)
         if self.exact_resume:
             torch.save(self._train_state(), train_state_path(path))
@@ -340,14 +455,23 @@ class OnPolicyRunner:
             raise ValueError(f"{path} was saved with empirical_normalization={'obs_norm_state_dict' in loaded}, this runner has "
                              f"empirical_normalization={self.empirical_normalization}: the policy's inputs would not be what it was trained on "
                              "(pass --empirical_normalization, or set train_cfg.runner.empirical_normalization, to match the checkpoint)")
+        if bool(loaded.get("privileged_actor", False)) != self.privileged_actor:
+            raise ValueError(f"{path} was saved with privileged_actor={bool(loaded.get('privileged_actor', False))}, this runner has "
+                             f"privileged_actor={self.privileged_actor}: the policy's inputs would not be what it was trained on "
+                             "(pass --privileged_actor, or set train_cfg.runner.privileged_actor, to match the checkpoint)")
         saved_hist = loaded.get("obs_history", {"actor": 1, "critic": 1})   # (a checkpoint without the key: no history)
+        if "distillation" in loaded and self.distillation is None:
+            return self._load_student(path, loaded, saved_hist)
+        if self.distillation is not None:
+            self._check_distillation_checkpoint(path, loaded)
         if (saved_hist["actor"], saved_hist["critic"]) != (self.obs_history_length, self.critic_obs_history_length):
             raise ValueError(f"{path} was saved with --obs_history {saved_hist['actor']} --critic_obs_history {saved_hist['critic']}, this runner has "
                              f"--obs_history {self.obs_history_length} --critic_obs_history {self.critic_obs_history_length}: the policy's inputs "
                              "would not be what it was trained on (pass the checkpoint's values, or set train_cfg.runner.obs_history_length / "
                              "critic_obs_history_length)")
         if self.empirical_normalization:
-            self.obs_normalizer.load_state_dict(loaded["obs_norm_state_dict"])
+            if self.obs_normalizer is not None:
+                self.obs_normalizer.load_state_dict(loaded["obs_norm_state_dict"])
             if self.critic_obs_normalizer is not None:
                 self.critic_obs_normalizer.load_state_dict(loaded["critic_obs_norm_state_dict"])
         self.algorithm.actor_critic.load_state_dict(loaded["model_state_dict"])
@@ -357,11 +481,52 @@ class OnPolicyRunner:
         self.current_learning_iteration = loaded["iter"]
         return loaded["infos"]
 
+    def _check_distillation_checkpoint(self, path, loaded):
+        """a distillation run resumes from a checkpoint of a distillation run with the same teacher only"""
+        if "distillation" not in loaded:
+            raise ValueError(f"{path} was not saved by a distillation run, this runner has distill_from={self.distill_from!r} "
+                             "(drop --distill_from to load a PPO checkpoint)")
+        if dict(loaded["distillation"]) != self.distillation:
+            raise ValueError(f"{path} was saved with distillation={loaded['distillation']}, this runner has {self.distillation} "
+                             "(pass the --distill_from / --distill_loss of the saved run)")
+        mine, sd = self.algorithm.actor_critic.state_dict(), loaded["model_state_dict"]
+        keys = [k for k in mine if k.startswith("teacher.")]
+        if sorted(k for k in sd if k.startswith("teacher.")) != sorted(keys) or \
+                any(sd[k].shape != mine[k].shape or not torch.equal(sd[k].to(mine[k].device), mine[k]) for k in keys):
+            raise ValueError(f"{path} was distilled from another teacher than {self.distill_from} (its teacher.* tensors differ): "
+                             "pass the --distill_from of the saved run")
+
+    def _load_student(self, path, loaded, saved_hist):
+        """a distilled checkpoint into an ordinary runner (play.py without --distill_from): the student's actor.*, std, the actor-side
+        normaliser and history; the critic stays what it is, the optimizer state is skipped"""
+        if saved_hist["actor"] != self.obs_history_length:
+            raise ValueError(f"{path} was saved with --obs_history {saved_hist['actor']} --critic_obs_history {saved_hist['critic']}, this runner has "
+                             f"--obs_history {self.obs_history_length} --critic_obs_history {self.critic_obs_history_length}: the policy's inputs "
+                             "would not be what it was trained on (pass the checkpoint's values, or set train_cfg.runner.obs_history_length / "
+                             "critic_obs_history_length)")
+        if self.empirical_normalization:
+            self.obs_normalizer.load_state_dict(loaded["obs_norm_state_dict"])
+        ac, sd = self.algorithm.actor_critic, loaded["model_state_dict"]
+        ac.actor.load_state_dict({k[len("actor."):]: v for k, v in sd.items() if k.startswith("actor.")})
+        with torch.no_grad():
+            ac.std.copy_(sd["std"])
+        self.algorithm.invalidate_graphs()
+        self.current_learning_iteration = loaded["iter"]
+        print(f"{path} is a distilled checkpoint: loaded the student's actor, std and actor-side normaliser / history; the critic is left as it "
+              "is and the optimizer state is skipped")
+        return loaded["infos"]
+
     def get_inference_policy(self, device=None):
         self.algorithm.actor_critic.eval()
         if device is not None:
             self.algorithm.actor_critic.to(device)
         policy = self.algorithm.actor_critic.act_inference
+        if self.privileged_actor:   # raw single PRIVILEGED frames in: the critic's history length and statistics
+            inner = self.algorithm.actor_critic.actor
+            if self.empirical_normalization:
+                self.critic_obs_normalizer.eval()
+                inner = NormalizedPolicy(inner, self.critic_obs_normalizer)
+            return HistoryPolicy(inner, self.env.num_pri_obs, self.critic_obs_history_length).to(device if device is not None else self.device)
         if self.empirical_normalization:   # raw observations in, as in training: normalised with the statistics as they are
             norm, act = self.obs_normalizer, self.algorithm.actor_critic.act_inference
             norm.eval()

@@ -63,14 +63,18 @@ def play(args, steps=None, log_root="default"):
     train_cfg.runner.resume = True
     ppo_runner, train_cfg = task_registry.make_alg_runner(env=env, name=args.task, args=args, train_cfg=train_cfg, log_root=log_root)
     policy = ppo_runner.get_inference_policy(device=env.device)
+    privileged = getattr(ppo_runner, "privileged_actor", False)   # (a teacher trained with --privileged_actor acts on the privileged frames)
+    if privileged:
+        obs = env.get_privileged_observations()
 
     exp_root = os.path.join(LEGGED_GYM_ROOT_DIR, "logs", train_cfg.runner.experiment_name) if log_root == "default" else log_root
     out_dir = os.path.join(exp_root, "exported")
     exported = None
     if EXPORT_POLICY:
         exported = export_policy_as_jit(ppo_runner.algorithm.actor_critic, out_dir,
-                                        normalizer=ppo_runner.obs_normalizer if ppo_runner.empirical_normalization else None,
-                                        history=ppo_runner.obs_history_length)
+                                        normalizer=(ppo_runner.critic_obs_normalizer if privileged else ppo_runner.obs_normalizer)
+                                        if ppo_runner.empirical_normalization else None,
+                                        history=ppo_runner.critic_obs_history_length if privileged else ppo_runner.obs_history_length)
         print(f"EXPORT_POLICY: Exported policy as jit script to: {exported}")
     os.makedirs(out_dir, exist_ok=True)
 
@@ -91,7 +95,9 @@ def play(args, steps=None, log_root="default"):
     with open(states_path, "w") as sf:
         for i in range(total):
             actions = policy(obs.detach())
-            obs, _, rews, dones, infos = env.step(actions.detach())
+            obs, pri, rews, dones, infos = env.step(actions.detach())
+            if privileged:
+                obs = pri
             if hasattr(policy, "reset"):   # (a policy with an observation history refills the rows of the envs that just ended)
                 policy.reset(dones)
 

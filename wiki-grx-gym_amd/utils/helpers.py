@@ -66,6 +66,12 @@ def get_args(argv=None):
                    help="The policy sees the last N observation frames, oldest first (1: off; saved in the checkpoint; play needs the same value)")
     p.add_argument("--critic_obs_history", type=int, default=1,
                    help="The critic sees the last N privileged observation frames (1: off; needs an env with privileged observations)")
+    p.add_argument("--privileged_actor", action="store_true", default=False,
+                   help="The actor reads the critic's input (privileged observations, --critic_obs_history): a teacher for --distill_from")
+    p.add_argument("--distill_from", type=str,
+                   help="Path of a PPO checkpoint: distil its actor into a student on the actor's observations (--obs_history) instead of running PPO")
+    p.add_argument("--distill_loss", type=str, choices=["mse", "huber"], help="Behaviour loss of --distill_from (default mse)")
+    p.add_argument("--distill_noise_std", type=float, help="Fixed action noise of the student's rollout under --distill_from (default 0.1)")
     args = p.parse_args(argv)
     if args.obs_history < 1 or args.critic_obs_history < 1:
         raise ValueError(f"--obs_history and --critic_obs_history must be >= 1, got {args.obs_history} and {args.critic_obs_history}")
@@ -108,6 +114,14 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
             cfg_train.runner.obs_history_length = int(args.obs_history)
         if getattr(args, "critic_obs_history", 1) != 1:   # (likewise)
             cfg_train.runner.critic_obs_history_length = int(args.critic_obs_history)
+        if getattr(args, "privileged_actor", False):   # (likewise)
+            cfg_train.runner.privileged_actor = True
+        if getattr(args, "distill_from", None) is not None:   # (likewise)
+            cfg_train.runner.distill_from = args.distill_from
+        if getattr(args, "distill_loss", None) is not None:   # (likewise)
+            cfg_train.runner.distill_loss = args.distill_loss
+        if getattr(args, "distill_noise_std", None) is not None:   # (likewise)
+            cfg_train.runner.distill_noise_std = float(args.distill_noise_std)
     return env_cfg, cfg_train
 
 
