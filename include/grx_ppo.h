@@ -190,6 +190,33 @@ int grx_distill_store(int N, int D, int A, const float* obs, const float* labels
                       float* st_obs, float* st_labels, unsigned char* st_dones,
                       float* cur_rew, float* cur_len, float* done_rew, float* done_len, void* stream);
 
+/* The LSTM cell of the recurrent actor-critic (legged_gym `ActorCriticRecurrent`, rsl_rl `Memory`; rl/recurrent.py).
+ * torch.nn.LSTM's formulas, gate order and weight layout, one layer:
+ *     G = x W_ih^T + h' W_hh^T + b_ih + b_hh        G = [i | f | g | o], each H wide
+ *     i, f, o = sigmoid(.)   g = tanh(.)            c = f c' + i g       h = o tanh(c)
+ * (h', c') = (h_prev, c_prev) of the row, or zero where the row's `reset` byte is non-zero: the rollout's done-reset is part of the
+ * next cell launch, there is no zeroing launch.
+ *   grx_lstm_cell: ONE launch.  x [M][D]; h_prev, c_prev, h, c [M][H]; reset [M] uint8 or NULL (no row is reset); W_ih [4H][D],
+ *                  W_hh [4H][H], b_ih, b_hh [4H]; acts [M][5H] or NULL: the four activated gates and tanh(c), [i | f | g | o | tanh c],
+ *                  what grx_lstm_cell_backward reads.  Out of place: h / c must not overlap h_prev / c_prev (the caller alternates two
+ *                  buffers, as with grx_obs_history_push).  Both products run on the f32 MFMA: every pre-activation is ONE fmaf chain
+ *                  from zero over x's columns in index order, then over h_prev's, then + b_ih, then + b_hh.  A row's result depends
+ *                  on that row's inputs alone: not on M, not on its neighbours.  No atomics.
+ *   grx_lstm_cell_preact: the test hook: the same reduction, G [M][4H] (biases added) written instead of h, c and acts.
+ *   grx_lstm_cell_backward: the element-wise half of the backward, one launch: from dh [M][H] (the gradient at h), dc_in [M][H] (the
+ *                  gradient arriving at c from the step after; NULL: zero), acts, c_prev and reset:
+ *                      do = dh tanh(c)     dc = dc_in + dh o (1 - tanh(c)^2)     di = dc g     dg = dc i     df = dc c'
+ *                      dG [M][4H] = [ di i (1 - i) | df f (1 - f) | dg (1 - g^2) | do o (1 - o) ]      dc_prev [M][H] = dc f
+ *                  with c' = 0 and dc_prev = 0 for a reset row (the caller zeroes those rows of dh_prev = dG W_hh likewise).
+ * Return 0, or negative with nothing launched and nothing written for M, D < 1, H no multiple of 32 in 32..1024, M * 5H >= 2^31, a NULL
+ * required pointer, or h / c overlapping h_prev / c_prev; negative for a failed launch. */
+int grx_lstm_cell(int M, int D, int H, const float* x, const float* h_prev, const float* c_prev, const unsigned char* reset,
+                  const float* W_ih, const float* W_hh, const float* b_ih, const float* b_hh, float* h, float* c, float* acts, void* stream);
+int grx_lstm_cell_preact(int M, int D, int H, const float* x, const float* h_prev, const unsigned char* reset, const float* W_ih,
+                         const float* W_hh, const float* b_ih, const float* b_hh, float* G, void* stream);
+int grx_lstm_cell_backward(int M, int H, const float* dh, const float* dc_in, const float* acts, const float* c_prev,
+                           const unsigned char* reset, float* dG, float* dc_prev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

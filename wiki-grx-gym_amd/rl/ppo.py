@@ -112,6 +112,12 @@ class PPO:
         # stream bookkeeping costs more than the overlap gives
         self._two_streams = self._use_graph and os.environ.get("GRX_PPO_TWO_STREAMS", "1") != "0"
         self._aux_stream = None
+        # a recurrent policy (rl/recurrent.py): the rollout's policy step and the minibatch step run eagerly, nothing is captured
+        self._recurrent = bool(getattr(actor_critic, "is_recurrent", False))
+        if self._recurrent:
+            if _world() > 1:
+                raise NotImplementedError("PPO: a recurrent policy trains in one process only")
+            self._use_graph = self._use_act_graph = self._two_streams = False
         if self._device_lr:
             # rsl_rl's `Normal.set_default_validate_args = False` (actor_critic.py) is an assignment, not a call, so the
             # reference validates (and host-syncs) on every Normal(); here the validation really is off
@@ -147,6 +153,11 @@ class PPO:
     def init_storage(self, num_envs, num_transitions_per_env, **_):
         ac = self.actor_critic
         self.transition = RolloutStorage.Transition()
+        if self._recurrent:
+            from .recurrent import RecurrentRolloutStorage
+            self.storage = RecurrentRolloutStorage(num_envs, num_transitions_per_env, [ac.num_actor_input], [ac.num_critic_input],
+                                                   [ac.num_actor_output], ac.rnn_hidden_size, self.device)
+            return
         self.storage = RolloutStorage(num_envs, num_transitions_per_env, [ac.num_actor_input], [ac.num_critic_input],
                                       [ac.num_actor_output], self.device)
 
@@ -245,10 +256,24 @@ class PPO:
 
     def act(self, actor_observations, critic_observations):
         t = self.transition
+        if self._recurrent:
+            return self._act_recurrent(actor_observations, critic_observations)
         if self._use_act_graph and actor_observations.is_cuda and not torch.is_grad_enabled():
             t.actions, t.values, t.actions_log_prob, t.action_mean, t.action_sigma = self._act_graphed(actor_observations, critic_observations)
         else:
             t.actions, t.values, t.actions_log_prob, t.action_mean, t.action_sigma = self._act_eager(actor_observations, critic_observations)
+        t.observations, t.critic_observations = actor_observations, critic_observations
+        return t.actions
+
+    def _act_recurrent(self, actor_observations, critic_observations):
+        """act() for a recurrent policy: both memories advance by one step (a cell launch each, the reset of the envs that just ended
+        folded in), then the two MLPs on the memories' outputs.  Eager."""
+        t, ac, st = self.transition, self.actor_critic, self.storage
+        if st.step == 0:   # what both memories start this rollout from: the update's forward starts there too
+            n, dev = actor_observations.shape[0], actor_observations.device
+            st.set_start_states(ac.memory_a.start_state(n, dev), ac.memory_c.start_state(n, dev))
+        with torch.no_grad():
+            t.actions, t.values, t.actions_log_prob, t.action_mean, t.action_sigma = ac.rollout_step(actor_observations, critic_observations)
         t.observations, t.critic_observations = actor_observations, critic_observations
         return t.actions
 
@@ -289,6 +314,10 @@ class PPO:
 
     def compute_returns(self, last_critic_obs):
         self._join_critic()
+        if self._recurrent:   # from the critic's memory as it is, into scratch: the memory does not advance
+            last_values = self.actor_critic.evaluate_bootstrap(last_critic_obs).detach()
+            self.storage.compute_returns(last_values, self.gamma, self.lam)
+            return
         last_values = self.actor_critic.evaluate(last_critic_obs).detach()
         self.storage.compute_returns(last_values, self.gamma, self.lam)
 
@@ -329,6 +358,8 @@ class PPO:
         lr.copy_(new)
 
     def update(self):
+        if self._recurrent:
+            return self._update_recurrent()
         if self._device_lr:
             # For these GEMM shapes (batch ~10^4 rows, 39..512 columns, fp32) rocBLAS's kernel choices beat hipBLASLt's by 2x
             # on the weight-gradient products dY^T X (27-48 us against 66-73 us, tools/gpu_gemm_probe.py).  torch's BLAS
@@ -383,6 +414,54 @@ class PPO:
             mean_surrogate_loss += surrogate_loss.item()
         self.num_updates = self.num_learning_epochs * self.num_mini_batches
         return mean_value_loss / self.num_updates, mean_surrogate_loss / self.num_updates
+
+    def _update_recurrent(self):
+        """update() for a recurrent policy: rsl_rl's recurrent_mini_batch_generator order (env ranges over all T steps, no permutation),
+        both memories run over the whole rollout from its stored start state (ActorCriticRecurrent.features), and the flattened outputs go
+        through _losses and the step's tail as they are.  Eager; on a HIP device without a host round trip inside the loop."""
+        ac = self.actor_critic
+        adaptive = self.desired_kl is not None and self.schedule == "adaptive"
+        sums = torch.zeros(3, device=self.device)        # value loss, surrogate loss, last KL
+        self.num_updates = self.num_learning_epochs * self.num_mini_batches
+        with self._blas_for_update() if self._device_lr else contextlib.nullcontext():
+            for (obs, cobs, resets, start, actions, target_values, advantages, returns, old_logp, old_mu, old_sigma) in \
+                    self.storage.recurrent_mini_batch_generator(self.num_mini_batches, self.num_learning_epochs):
+                fa, fc = ac.features(obs, cobs, resets, start)
+                with ac.on_features():
+                    surrogate_loss, value_loss, loss, kl_mean = self._losses(fa, fc, actions, target_values, advantages, returns,
+                                                                              old_logp, old_mu, old_sigma)
+                if not self._device_lr:
+                    if adaptive:
+                        self._apply_kl(kl_mean.item())
+                    if not torch.isfinite(loss):
+                        continue
+                    self.optimizer.zero_grad()
+                    loss.backward()
+                    nn.utils.clip_grad_norm_(ac.parameters(), self.max_grad_norm)
+                    self.optimizer.step()
+                    sums[0] += value_loss.detach(); sums[1] += surrogate_loss.detach()
+                    continue
+                self.optimizer.zero_grad(set_to_none=False)
+                loss.backward()
+                if self._step_tail(loss, kl_mean, value_loss, surrogate_loss, sums, adaptive):
+                    continue
+                if adaptive:
+                    self._device_lr_update(kl_mean)
+                with torch.no_grad():
+                    bad = ~torch.isfinite(loss)
+                    self.optimizer.found_inf = bad.float().reshape(())   # NaN-skip (ppo.py:297-299) through fused Adam's hook
+                    self.optimizer.grad_scale = None
+                nn.utils.clip_grad_norm_(ac.parameters(), self.max_grad_norm, foreach=True)
+                self.optimizer.step()
+                with torch.no_grad():
+                    sums[0] += torch.where(bad, 0.0, value_loss.detach())   # (a skipped step adds nothing)
+                    sums[1] += torch.where(bad, 0.0, surrogate_loss.detach())
+                    sums[2] = kl_mean
+        host = sums.tolist()                           # the only device->host transfer of the update on a HIP device
+        if self._device_lr:
+            self.mean_kl = host[2]
+            self.learning_rate = float(self._lr_t.item())
+        return host[0] / self.num_updates, host[1] / self.num_updates
 
     @contextlib.contextmanager
     def _blas_for_update(self):

@@ -23,9 +23,10 @@ from .history import HistoryPolicy, ObsHistory
 from .modules import ActorCriticMLP
 from .normalizer import EmpiricalNormalization, NormalizedPolicy, normalize_step
 from .ppo import PPO
+from .recurrent import ActorCriticRecurrent, RecurrentPolicy
 from .storage import RolloutStorage  # noqa: F401
 
-_POLICIES = {"ActorCriticMLP": ActorCriticMLP, "ActorCritic": ActorCriticMLP}
+_POLICIES = {"ActorCriticMLP": ActorCriticMLP, "ActorCritic": ActorCriticMLP, "ActorCriticRecurrent": ActorCriticRecurrent}
 _ALGORITHMS = {"PPO": PPO, "Distillation": Distillation}
 
 
@@ -76,6 +77,11 @@ class OnPolicyRunner:
         self._alt_inputs = None    # what builds (actor input, critic-slot input) from one step's raw frames in these two modes
         if self.privileged_actor:
             self._check_privileged_actor(env)
+        # a recurrent policy: an LSTM in front of the actor's and the critic's MLP.  Not config keys either (`--recurrent` /
+        # `--rnn_hidden_size` or assignments to train_cfg.runner.policy_class_name / train_cfg.policy.rnn_hidden_size set them)
+        self.recurrent = bool(getattr(policy_cls, "is_recurrent", False))
+        if self.recurrent:
+            self._check_recurrent()
         if self.distill_from is not None:
             teacher = self._check_distillation(env, device)
         self.obs_history = self.critic_obs_history = None
@@ -304,6 +310,22 @@ class OnPolicyRunner:
         if self.distill_from is not None:
             raise ValueError("privileged_actor and distill_from exclude each other: the student reads the actor's observations")
 
+    def _check_recurrent(self):
+        """what a recurrent policy (--recurrent) does not combine with"""
+        if self.obs_history_length != 1 or self.critic_obs_history_length != 1:
+            raise ValueError(f"--recurrent with --obs_history {self.obs_history_length} --critic_obs_history {self.critic_obs_history_length}: the "
+                             "memory replaces the frame stack (drop one of the two options)")
+        if self.privileged_actor:
+            raise ValueError("--recurrent and --privileged_actor exclude each other: a recurrent teacher is not implemented")
+        if self.distill_from is not None:
+            raise NotImplementedError("--recurrent with --distill_from: a recurrent student is not implemented (distillation trains an MLP student)")
+        if self.algorithm_cfg.get("precision", "fp32") != "fp32":
+            raise ValueError(f"--recurrent with --precision {self.algorithm_cfg['precision']}: the recurrent policy runs in fp32")
+        if bool(self.cfg.get("exact_resume", False)):
+            raise NotImplementedError("--recurrent with --exact_resume: the memories' state is not part of train_state_<it>.pt")
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("--recurrent with a world size above 1: a recurrent policy trains in one process only")
+
     def _check_distillation(self, env, device):
         """the refusals of a distillation run; returns what the checkpoint at distill_from says about its actor (distillation.read_teacher)"""
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
@@ -388,6 +410,8 @@ class OnPolicyRunner:
             saved["privileged_actor"] = True
         if self.distillation is not None:   # (likewise)
             saved["distillation"] = dict(self.distillation)
+        if self.recurrent:   # (likewise)
+            saved["recurrent"] = {"hidden_size": self.algorithm.actor_critic.rnn_hidden_size}
         torch.save(saved, path)
         if self.exact_resume:
             torch.save(self._train_state(), train_state_path(path))
@@ -459,6 +483,11 @@ class OnPolicyRunner:
             raise ValueError(f"{path} was saved with privileged_actor={bool(loaded.get('privileged_actor', False))}, this runner has "
                              f"privileged_actor={self.privileged_actor}: the policy's inputs would not be what it was trained on "
                              "(pass --privileged_actor, or set train_cfg.runner.privileged_actor, to match the checkpoint)")
+        mine = {"hidden_size": self.algorithm.actor_critic.rnn_hidden_size} if self.recurrent else None
+        if loaded.get("recurrent") != mine:
+            raise ValueError(f"{path} was saved with recurrent={loaded.get('recurrent')}, this runner has recurrent={mine}: the policy would not "
+                             "be the one that was trained (pass --recurrent --rnn_hidden_size H, or set train_cfg.runner.policy_class_name / "
+                             "train_cfg.policy.rnn_hidden_size, to match the checkpoint)")
         saved_hist = loaded.get("obs_history", {"actor": 1, "critic": 1})   # (a checkpoint without the key: no history)
         if "distillation" in loaded and self.distillation is None:
             return self._load_student(path, loaded, saved_hist)
@@ -521,6 +550,14 @@ class OnPolicyRunner:
         if device is not None:
             self.algorithm.actor_critic.to(device)
         policy = self.algorithm.actor_critic.act_inference
+        if self.recurrent:   # raw frames in: a memory state of its own (policy.reset(dones) after every env.step, policy.reset_memory())
+            norm = None
+            if self.empirical_normalization:
+                norm = self.obs_normalizer
+                norm.eval()
+                if device is not None:
+                    norm.to(device)
+            return RecurrentPolicy(self.algorithm.actor_critic, norm)
         if self.privileged_actor:   # raw single PRIVILEGED frames in: the critic's history length and statistics
             inner = self.algorithm.actor_critic.actor
             if self.empirical_normalization:

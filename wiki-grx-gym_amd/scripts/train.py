@@ -1,6 +1,7 @@
 """train.py -- same three lines of logic as the reference (legged_gym/scripts/train.py:40-43).
 
     python -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless --num_envs 4096
+    python -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless --recurrent --rnn_hidden_size 256     (an LSTM policy: DESIGN.md 4.10)
     torchrun --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless
 """
 import os

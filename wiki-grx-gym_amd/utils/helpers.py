@@ -72,6 +72,9 @@ def get_args(argv=None):
                    help="Path of a PPO checkpoint: distil its actor into a student on the actor's observations (--obs_history) instead of running PPO")
     p.add_argument("--distill_loss", type=str, choices=["mse", "huber"], help="Behaviour loss of --distill_from (default mse)")
     p.add_argument("--distill_noise_std", type=float, help="Fixed action noise of the student's rollout under --distill_from (default 0.1)")
+    p.add_argument("--recurrent", action="store_true", default=False,
+                   help="A recurrent policy: an LSTM in front of the actor's and the critic's MLP (saved in the checkpoint; play needs the same flag)")
+    p.add_argument("--rnn_hidden_size", type=int, default=256, help="Hidden size of --recurrent's LSTMs: a multiple of 32 in 32..1024")
     args = p.parse_args(argv)
     if args.obs_history < 1 or args.critic_obs_history < 1:
         raise ValueError(f"--obs_history and --critic_obs_history must be >= 1, got {args.obs_history} and {args.critic_obs_history}")
@@ -122,6 +125,9 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
             cfg_train.runner.distill_loss = args.distill_loss
         if getattr(args, "distill_noise_std", None) is not None:   # (likewise)
             cfg_train.runner.distill_noise_std = float(args.distill_noise_std)
+        if getattr(args, "recurrent", False):   # (likewise: the policy config has no rnn_hidden_size otherwise)
+            cfg_train.runner.policy_class_name = "ActorCriticRecurrent"
+            cfg_train.policy.rnn_hidden_size = int(getattr(args, "rnn_hidden_size", 256))
     return env_cfg, cfg_train
 
 
@@ -156,11 +162,17 @@ def get_load_path(root, load_run=-1, checkpoint=-1):
 
 
 def export_policy_as_jit(actor_critic, path, normalizer=None, history=1):
-    """`normalizer` (an rl.normalizer.EmpiricalNormalization): the exported module takes RAW observations and normalises them itself.
+    """A recurrent actor_critic (rl.recurrent.ActorCriticRecurrent): the exported module is an nn.LSTM with its state in buffers in front
+    of the actor's layers (rl.recurrent.ExportedRecurrentPolicy: one raw frame per call, `reset_memory()` and `reset(dones)` exported).
+    `normalizer` (an rl.normalizer.EmpiricalNormalization): the exported module takes RAW observations and normalises them itself.
     `history` > 1 (the runner's obs_history_length): it takes raw SINGLE frames and keeps the last `history` of them itself
     (rl.history.HistoryPolicy: `reset_memory()` and `reset(dones)` are exported methods)"""
     os.makedirs(path, exist_ok=True)
     path = os.path.join(path, "policy_jit.pt")
+    if getattr(actor_critic, "is_recurrent", False):
+        from ..rl.recurrent import ExportedRecurrentPolicy
+        torch.jit.script(ExportedRecurrentPolicy(actor_critic, normalizer)).save(path)
+        return path
     model = copy.deepcopy(actor_critic.actor).to("cpu")
     if normalizer is not None:
         from ..rl.normalizer import NormalizedPolicy
