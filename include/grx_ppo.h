@@ -217,6 +217,27 @@ int grx_lstm_cell_preact(int M, int D, int H, const float* x, const float* h_pre
 int grx_lstm_cell_backward(int M, int H, const float* dh, const float* dc_in, const float* acts, const float* c_prev,
                            const unsigned char* reset, float* dG, float* dc_prev, void* stream);
 
+/* The minibatch of one PPO step WITH its mirror image (rsl_rl 2.x `symmetry_cfg`; rl/symmetry.py): grx_ppo_gather_rows's
+ * contract -- host arrays of device pointers, at most GRX_PPO_GATHER_MAX tensors, idx int64 on the device -- with a second half.  For
+ * every tensor t and r < mb, with s = idx[r] (idx == NULL: s = r, the stand-alone "mirror these rows" call):
+ *     dst[t][r][:]      = src[t][s][:]
+ *     dst[t][mb + r][j] = modes[t] == 2:  fmaf(scale[t][j], src[t][s][perm[t][j]], offset[t][j])   (offset[t] or offset NULL: a plain product)
+ *                         modes[t] == 1:  src[t][s][j]                                              (values, advantages, returns, old_logp)
+ *                         modes[t] == 0:  not written: dst[t] has mb rows only
+ * modes / perm / scale / offset are HOST arrays of n_tensors entries; perm[t] int32 [widths[t]], scale[t] / offset[t] fp32 [widths[t]] on
+ * the device, read by mode 2 only (perm, scale, offset and their entries may be NULL where no tensor needs them).  src[t] and dst[t] must
+ * not overlap.  ONE launch: a block stages its tensor's map and four source rows in LDS, (3 + 4) * 4 bytes per column of the widest tensor,
+ * so a width is at most GRX_SYM_MAX_WIDTH = 2048 (56 KiB): 12 stacked privileged frames of 168 columns.  Pure copies and one fmaf per
+ * element, no atomics: deterministic, and a row's result does not depend on mb.  The kernel trusts the maps: a perm entry outside
+ * 0..widths[t]-1 is refused where the maps are built (rl/symmetry.py).
+ * Returns 0, or negative with nothing launched and nothing written for mb < 1, n_tensors outside 1..GRX_PPO_GATHER_MAX, a width outside
+ * 1..GRX_SYM_MAX_WIDTH, a mode outside 0..2, mode 2 without perm[t] / scale[t], a NULL src / dst / widths / modes or entry of src / dst;
+ * negative for a failed launch. */
+#define GRX_SYM_MAX_WIDTH 2048
+int grx_sym_gather_rows(int n_tensors, const float* const* src, float* const* dst, const int* widths, const int* modes,
+                        const int* const* perm, const float* const* scale, const float* const* offset, const long long* idx, int mb,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

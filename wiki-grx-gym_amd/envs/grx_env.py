@@ -289,6 +289,28 @@ class GRxEnv:
     def get_privileged_observations(self):
         return self.pri_obs_buf
 
+    # ------------------------------------------------------------------ left-right mirror (rl/symmetry.py)
+    def _mirror_maps(self):
+        """(observation map, privileged observation map or None, joint map) on the env's device, built once from the joint names and the
+        height scan's layout; raises ValueError for a robot or a scan the maps do not cover"""
+        if getattr(self, "_mirror", None) is None:
+            from ..rl.symmetry import MirrorMap, env_maps
+            frame, pri, J = env_maps(self)
+            dev = self._sim.device
+            self._mirror = (MirrorMap(*frame, dev, "observation map"), MirrorMap(*pri, dev, "privileged observation map") if pri is not None else None,
+                            MirrorMap(*J, dev, "joint map"))
+        return self._mirror
+
+    def reflect_dof_prop(self, x):
+        """the left-right mirror image of a per-joint tensor (N, num_dof): partners swapped, roll and yaw joints negated (the name the
+        reference's runner calls under symmetry_coef > 0)"""
+        return self._mirror_maps()[2](x)
+
+    def get_reflection_observations(self):
+        """the mirror image of the current observations: (obs, pri_obs or None) (likewise)"""
+        obs_map, pri_map, _ = self._mirror_maps()
+        return obs_map(self.obs_buf), (pri_map(self.pri_obs_buf) if pri_map is not None else None)
+
     def step(self, actions):
         """legged_robot.py:222-246 -- one fused kernel launch."""
         a = actions.to(device=self._sim.device, dtype=torch.float32)

@@ -76,6 +76,10 @@ def load_ppo_library():
         lib.grx_distill_loss.argtypes = [C.c_int, C.c_int, fp, fp, C.c_int, fp, fp, fp, C.c_void_p]
         lib.grx_distill_store.restype = C.c_int
         lib.grx_distill_store.argtypes = [C.c_int] * 3 + [fp] * 11 + [C.c_void_p]
+        # left-right symmetry (rl/symmetry.py)
+        pp = C.POINTER(C.c_void_p)
+        lib.grx_sym_gather_rows.restype = C.c_int
+        lib.grx_sym_gather_rows.argtypes = [C.c_int, pp, pp, C.POINTER(C.c_int), C.POINTER(C.c_int), pp, pp, pp, fp, C.c_int, C.c_void_p]
         _LIB = lib
     return _LIB
 
@@ -392,3 +396,68 @@ class RowGather:
                                               torch.cuda.current_stream(self.device).cuda_stream)
         if rc:
             raise RuntimeError(f"grx_ppo_gather_rows failed ({rc})")
+
+
+class SymGather:
+    """RowGather with the minibatch's mirror image behind it (grx_sym_gather_rows, rl/symmetry.py): dst[t][:mb] = src[t][idx] and
+    dst[t][mb:] = that again (modes[t] == 1), its mirror image under maps[t] (2) or nothing (0: dst[t] has mb rows), for a fixed set of
+    (src, dst) pairs in one launch.  The pointer tables are built once: the maps' tensors are rewritten in place, never replaced.
+    idx None: row r itself (the stand-alone "mirror these rows" call)."""
+
+    def __init__(self, srcs, dsts, modes, maps):
+        self.lib = load_ppo_library()
+        n = len(srcs)
+        assert n == len(dsts) == len(modes) == len(maps)
+        rows = [d.shape[0] // (2 if m else 1) for d, m in zip(dsts, modes)]
+        assert all(s.dtype == torch.float32 and s.is_contiguous() and d.is_contiguous() and d.dtype == torch.float32 and s.shape[1:] == d.shape[1:]
+                   and d.shape[0] == r * (2 if m else 1) and r == rows[0] for s, d, m, r in zip(srcs, dsts, modes, rows))
+        self.n, self.mb, self.device = n, rows[0], srcs[0].device
+        self.src = (C.c_void_p * n)(*[s.data_ptr() for s in srcs])
+        self.dst = (C.c_void_p * n)(*[d.data_ptr() for d in dsts])
+        self.w = (C.c_int * n)(*[int(s[0].numel()) for s in srcs])
+        self.modes = (C.c_int * n)(*[int(m) for m in modes])
+        for m, mp, w in zip(modes, maps, self.w):
+            assert m != 2 or (mp is not None and mp.width == w and mp.perm.dtype == torch.int32 and mp.perm.is_contiguous()
+                              and mp.scale.dtype == torch.float32 and mp.scale.is_contiguous()
+                              and (mp.offset is None or (mp.offset.dtype == torch.float32 and mp.offset.is_contiguous())))
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        self.perm = (C.c_void_p * n)(*[ptr(mp.perm) if m == 2 else None for m, mp in zip(modes, maps)])
+        self.scale = (C.c_void_p * n)(*[ptr(mp.scale) if m == 2 else None for m, mp in zip(modes, maps)])
+        self.offset = (C.c_void_p * n)(*[ptr(mp.offset) if m == 2 else None for m, mp in zip(modes, maps)])
+        self.keep = (srcs, dsts, maps)
+
+    def __call__(self, idx=None):
+        assert idx is None or (idx.dtype == torch.int64 and idx.is_contiguous() and idx.numel() == self.mb)
+        with torch.cuda.device(self.device):
+            rc = self.lib.grx_sym_gather_rows(self.n, self.src, self.dst, self.w, self.modes, self.perm, self.scale, self.offset,
+                                              idx.data_ptr() if idx is not None else None, self.mb,
+                                              torch.cuda.current_stream(self.device).cuda_stream)
+        if rc:
+            raise RuntimeError(f"grx_sym_gather_rows failed ({rc})")
+
+
+class MirrorRows:
+    """x [rows, W] -> mirror(x) under one map, through grx_sym_gather_rows without an index (the stand-alone "mirror these rows" call): the
+    output buffer and the pointer tables are built once, a call sets the source pointer.  The entry point's contract writes the rows
+    themselves in front of their mirror image; what is handed out is the second half.  The result is overwritten by the next call."""
+
+    def __init__(self, rows, m, device):
+        self.lib = load_ppo_library()
+        assert m.perm.dtype == torch.int32 and m.perm.is_contiguous() and m.scale.dtype == torch.float32 and m.scale.is_contiguous()
+        self.rows, self.map, self.device = int(rows), m, device
+        self.dst = torch.empty(2 * self.rows, m.width, device=device)
+        self.src = (C.c_void_p * 1)(None)
+        self.dstp = (C.c_void_p * 1)(self.dst.data_ptr())
+        self.w, self.modes = (C.c_int * 1)(m.width), (C.c_int * 1)(2)
+        self.perm, self.scale = (C.c_void_p * 1)(m.perm.data_ptr()), (C.c_void_p * 1)(m.scale.data_ptr())
+        self.offset = (C.c_void_p * 1)(m.offset.data_ptr() if m.offset is not None else None)
+
+    def __call__(self, x):
+        assert x.dtype == torch.float32 and x.is_contiguous() and tuple(x.shape) == (self.rows, self.map.width) and x.device == self.dst.device
+        self.src[0] = x.data_ptr()
+        with torch.cuda.device(self.device):
+            rc = self.lib.grx_sym_gather_rows(1, self.src, self.dstp, self.w, self.modes, self.perm, self.scale, self.offset, None, self.rows,
+                                              torch.cuda.current_stream(self.device).cuda_stream)
+        if rc:
+            raise RuntimeError(f"grx_sym_gather_rows failed ({rc})")
+        return self.dst[self.rows:]

@@ -62,7 +62,8 @@ class PPO:
     def __init__(self, actor_critic=None, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998, lam=0.95,
                  value_loss_coef=1.0, entropy_coef=0.0, learning_rate=1e-3, learning_rate_min=1e-5, learning_rate_max=1e-2,
                  weight_decay=0.0, max_grad_norm=1.0, use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01,
-                 device="cpu", storage_class="RolloutStorage", precision="fp32", **kwargs):
+                 device="cpu", storage_class="RolloutStorage", precision="fp32", symmetry=None, symmetry_coef=1.0, symmetry_maps=None,
+                 **kwargs):
         if kwargs:
             print("PPO.__init__ got unexpected arguments, which will be ignored: " + str(list(kwargs)))
         # precision="bf16": every hidden layer of actor and critic multiplies bf16 operands into fp32 accumulators -- in the rollout's
@@ -130,7 +131,12 @@ class PPO:
         self.clip_param, self.num_learning_epochs, self.num_mini_batches = clip_param, num_learning_epochs, num_mini_batches
         self.value_loss_coef, self.entropy_coef, self.gamma, self.lam = value_loss_coef, entropy_coef, gamma, lam
         self.max_grad_norm, self.use_clipped_value_loss = max_grad_norm, use_clipped_value_loss
-        self.symmetry_coef = 0
+        # left-right symmetry (rl/symmetry.py): "augment" extends every minibatch by its mirror image, "loss" adds
+        # symmetry_coef * mse(actor(mirror(obs)), mirror(actor(obs)).detach()), "both" does both.  Not a config key: `--symmetry` /
+        # `--symmetry_coef` or an assignment to train_cfg.algorithm sets it; None runs nothing of it
+        self.symmetry, self._sym, self.symmetry_coef, self.mean_symmetry_loss = None, None, 0, 0.0
+        if symmetry is not None:
+            self._init_symmetry(symmetry, symmetry_coef, symmetry_maps)
         self.num_updates = 0
         self._params = [p for p in self.actor_critic.parameters() if p.requires_grad]
         n = sum(p.numel() for p in self._params)
@@ -149,6 +155,28 @@ class PPO:
     def _install_flat_grads(self):
         for p, o in zip(self._params, self._offsets()):
             p.grad = self._bucket[o:o + p.numel()].view_as(p)
+
+    def _init_symmetry(self, symmetry, symmetry_coef, maps):
+        from .symmetry import MODES
+        if symmetry not in MODES:
+            raise ValueError(f"PPO: symmetry must be None or one of {MODES}, not {symmetry!r}")
+        if self._recurrent:
+            raise ValueError("PPO: --symmetry and --recurrent exclude each other: a mirrored minibatch of a recurrent policy is not implemented")
+        if _world() > 1:
+            raise NotImplementedError("PPO: --symmetry with a world size above 1 is not implemented: it trains in one process only")
+        if maps is None:
+            raise ValueError(f"PPO: symmetry={symmetry!r} needs symmetry_maps (rl.symmetry.build_maps(env, ...))")
+        ac = self.actor_critic
+        if (maps.obs.width, maps.cobs.width, maps.actions.width) != (ac.num_actor_input, ac.num_critic_input, ac.num_actor_output):
+            raise ValueError(f"PPO: the symmetry maps are {maps.obs.width} / {maps.cobs.width} / {maps.actions.width} columns wide, the policy's actor "
+                             f"input / critic input / actions {ac.num_actor_input} / {ac.num_critic_input} / {ac.num_actor_output}")
+        self.symmetry, self._sym = symmetry, maps
+        self.symmetry_coef = float(symmetry_coef) if symmetry in ("loss", "both") else 0
+        self._sym_sum = torch.zeros(1, device=self.device)     # the update's sum of mirror losses (finite steps), read back once per update
+        self._sym_bufs, self._sym_bufs_gather, self._sym_mirror = None, None, None
+        # the nine minibatch tensors (obs, cobs, actions, values, advantages, returns, old_logp, old_mu, old_sigma): how each gets its second half
+        self._sym_modes = [2, 2, 2, 1, 1, 1, 1, 2, 2] if symmetry in ("augment", "both") else [2, 0, 0, 0, 0, 0, 0, 0, 0]
+        self._sym_tensor_maps = [maps.obs, maps.cobs, maps.actions, None, None, None, None, maps.actions, maps.sigma]
 
     def init_storage(self, num_envs, num_transitions_per_env, **_):
         ac = self.actor_critic
@@ -360,6 +388,8 @@ class PPO:
     def update(self):
         if self._recurrent:
             return self._update_recurrent()
+        if self.symmetry is not None:
+            return self._update_symmetry()
         if self._device_lr:
             # For these GEMM shapes (batch ~10^4 rows, 39..512 columns, fp32) rocBLAS's kernel choices beat hipBLASLt's by 2x
             # on the weight-gradient products dY^T X (27-48 us against 66-73 us, tools/gpu_gemm_probe.py).  torch's BLAS
@@ -478,35 +508,51 @@ class PPO:
         """(surrogate_loss, value_loss, loss, kl_mean) of one minibatch -- ppo.py:215-245.
 
         On a HIP device: the actor / critic forward in torch, everything after it in ONE kernel that also produces the
-        gradients (rl/fused_loss.py -> libgrx_ppo.so; GRX_PPO_FUSED_LOSS=0 keeps the torch expression below)."""
+        gradients (rl/fused_loss.py -> libgrx_ppo.so; GRX_PPO_FUSED_LOSS=0 keeps the torch expression of _loss_terms)."""
+        mu, value = self._forward(obs, cobs)
+        return self._loss_terms(mu, value, actions, target_values, advantages, returns, old_logp, old_mu, old_sigma)
+
+    def _loss_is_fused(self):
+        ac = self.actor_critic
+        return self._fused_loss and not ac.fixed_std and ac.num_actor_output <= 32   # the kernel's action-count limit
+
+    def _forward(self, obs, cobs):
+        """(mu, value): the actor's and the critic's forward of one minibatch"""
+        ac = self.actor_critic
+        if not self._loss_is_fused():
+            ac.update_distribution(obs)   # (the torch spelling in _loss_terms reads sigma from the distribution)
+            return ac.action_mean, ac.evaluate(cobs)
+        # (only while the actor's GEMMs go to rocBLAS -- update() / _build_graph's preference: with torch's default hipBLASLt on BOTH
+        #  streams, the value head's weight gradient at minibatch 49152 came out wrong once and the step did not finish twice)
+        if self._two_streams and torch.backends.cuda.preferred_blas_library() == torch._C._BlasBackend.Cublas:
+            # actor and critic are independent until the loss: the critic's forward (and, through autograd's stream
+            # bookkeeping, its backward) runs on a second stream
+            cur = torch.cuda.current_stream(self.device)
+            if self._aux_stream is None:
+                self._aux_stream = torch.cuda.Stream(device=self.device)
+            self._aux_stream.wait_stream(cur)
+            with torch.cuda.stream(self._aux_stream):
+                value = ac.evaluate(cobs)
+            mu = ac.actor(obs)
+            cur.wait_stream(self._aux_stream)
+            value.record_stream(cur)
+            return mu, value
+        mu = ac.actor(obs)
+        return mu, ac.evaluate(cobs)
+
+    def _loss_terms(self, mu, value, actions, target_values, advantages, returns, old_logp, old_mu, old_sigma):
+        """(surrogate_loss, value_loss, loss, kl_mean) from _forward's outputs; mu may be the first rows of what the actor returned
+        (symmetry "loss": the mirrored rows behind them have no PPO loss)"""
         ac = self.actor_critic
         adaptive = self.desired_kl is not None and self.schedule == "adaptive"
-        if self._fused_loss and not ac.fixed_std and ac.num_actor_output <= 32:   # the kernel's action-count limit
-            # (only while the actor's GEMMs go to rocBLAS -- update() / _build_graph's preference: with torch's default hipBLASLt on BOTH
-            #  streams, the value head's weight gradient at minibatch 49152 came out wrong once and the step did not finish twice)
-            if self._two_streams and torch.backends.cuda.preferred_blas_library() == torch._C._BlasBackend.Cublas:
-                # actor and critic are independent until the loss: the critic's forward (and, through autograd's stream
-                # bookkeeping, its backward) runs on a second stream
-                cur = torch.cuda.current_stream(self.device)
-                if self._aux_stream is None:
-                    self._aux_stream = torch.cuda.Stream(device=self.device)
-                self._aux_stream.wait_stream(cur)
-                with torch.cuda.stream(self._aux_stream):
-                    value = ac.evaluate(cobs)
-                mu = ac.actor(obs)
-                cur.wait_stream(self._aux_stream)
-                value.record_stream(cur)
-            else:
-                mu = ac.actor(obs)
-                value = ac.evaluate(cobs)
+        if self._loss_is_fused():
             out = fused_ppo_loss(mu, ac.std, value, actions, old_logp, old_mu, old_sigma, advantages, returns, target_values,
                                  self.clip_param, self.value_loss_coef, self.entropy_coef, self.use_clipped_value_loss)
             kl_mean = out[3].detach() if adaptive else torch.zeros((), device=self.device)
             return out[0], out[1], out[2], kl_mean
-        ac.update_distribution(obs)
-        logp = ac.get_actions_log_prob(actions)
-        value = ac.evaluate(cobs)
-        mu, sigma, entropy = ac.action_mean, ac.action_std, ac.entropy
+        sigma = ac.action_std[:mu.shape[0]]
+        dist_ = torch.distributions.Normal(mu, sigma, validate_args=False)
+        logp, entropy = dist_.log_prob(actions).sum(dim=-1), dist_.entropy().sum(dim=-1)
         kl_mean = torch.zeros((), device=self.device)
         if adaptive:
             with torch.no_grad():
@@ -522,6 +568,110 @@ class PPO:
             value_loss = (returns - value).pow(2).mean()
         loss = surrogate_loss + self.value_loss_coef * value_loss - self.entropy_coef * entropy.mean()
         return surrogate_loss, value_loss, loss, kl_mean
+
+    # ------------------------------------------------------------------ left-right symmetry (rl/symmetry.py)
+    def _sym_gatherer(self, srcs, dsts):
+        """idx -> the minibatch with its mirrored half in dsts: one launch of grx_sym_gather_rows on a HIP device (GRX_SYM_FUSED=0, CPU
+        tensors: rl.symmetry.sym_gather_torch, the same arithmetic in torch)"""
+        from .symmetry import fused_enabled, sym_gather_torch
+        if srcs[0].is_cuda and fused_enabled():
+            from .fused_loss import SymGather
+            return SymGather(srcs, dsts, self._sym_modes, self._sym_tensor_maps)
+        return lambda idx: sym_gather_torch(srcs, dsts, self._sym_modes, self._sym_tensor_maps, idx)
+
+    def _mirror_actions(self, mu):
+        """mirror_actions(mu) for mu [mb, A] (detached): one grx_sym_gather_rows call without an index on a HIP device, through a
+        MirrorRows kept per shape (its pointer tables and its output buffer are built once)"""
+        from .symmetry import fused_enabled
+        m = self._sym.actions
+        if not (mu.is_cuda and fused_enabled()):
+            return m(mu)
+        key = (tuple(mu.shape), mu.device)
+        if self._sym_mirror is None or self._sym_mirror[0] != key:
+            from .fused_loss import MirrorRows
+            self._sym_mirror = (key, MirrorRows(mu.shape[0], m, mu.device))
+        return self._sym_mirror[1](mu)
+
+    def _losses_sym(self, obs, cobs, actions, target_values, advantages, returns, old_logp, old_mu, old_sigma):
+        """_losses on a minibatch whose second half is the mirror image of its first (symmetry "augment" / "both": every tensor has
+        2 mb rows; "loss": obs alone, the PPO loss and the critic see the mb rows there are), plus the mirror loss
+        mse(mu[mb:], mirror_actions(mu[:mb]).detach()) through grx_distill_loss: added to the loss with symmetry_coef ("loss" / "both"),
+        logged only ("augment")."""
+        from .distillation import distill_loss
+        mb, n = obs.shape[0] // 2, actions.shape[0]   # rows of the unmirrored half; rows the PPO loss sees
+        mu, value = self._forward(obs, cobs)
+        surrogate_loss, value_loss, loss, kl_mean = self._loss_terms(mu[:n], value, actions, target_values, advantages, returns,
+                                                                     old_logp, old_mu, old_sigma)
+        with torch.no_grad():
+            target = self._mirror_actions(mu[:mb].detach())
+        if self.symmetry == "augment":
+            with torch.no_grad():
+                sym = distill_loss(mu[mb:].detach(), target, "mse")
+        else:
+            sym = distill_loss(mu[mb:], target, "mse")
+            loss = loss + self.symmetry_coef * sym
+        with torch.no_grad():   # (a step the NaN-skip drops adds nothing, as with the other statistics)
+            s = sym.detach().reshape(1)
+            self._sym_sum += torch.where(torch.isfinite(loss.detach()).reshape(1), s, torch.zeros_like(s))
+        return surrogate_loss, value_loss, loss, kl_mean
+
+    def _sym_sources(self):
+        st = self.storage
+        flat = lambda x: x.flatten(0, 1)
+        cobs = st.pri_observations if st.pri_observations is not None else st.observations
+        return [flat(x) for x in (st.observations, cobs, st.actions, st.values, st.advantages, st.returns, st.actions_log_prob, st.mu, st.sigma)]
+
+    def _update_symmetry(self):
+        """update() with symmetry on: the maps take the normalisers' statistics as they are now (in place), every minibatch is gathered
+        WITH its mirrored half into fixed buffers, and the step is the captured one, the eager device one or the CPU one below"""
+        self._sym.refresh()
+        self._sym_sum.zero_()
+        if self._device_lr:
+            with self._blas_for_update():
+                out = self._update_graphed() if self._use_graph else self._update_sym_eager()
+        else:
+            out = self._update_sym_eager()
+        self.mean_symmetry_loss = float(self._sym_sum.item()) / self.num_updates   # one extra 4-byte read-back per update
+        return out
+
+    def _update_sym_eager(self):
+        """the eager paths: on a HIP device _update_graphed's loop with the step run, not replayed (the arithmetic of _update_device);
+        on the CPU update()'s host-side adaptive learning rate, NaN-skip, clip and Adam"""
+        st = self.storage
+        mb = st.num_envs * st.num_transitions_per_env // self.num_mini_batches
+        srcs = self._sym_sources()
+        if self._sym_bufs is None or self._sym_bufs[0].shape[0] != 2 * mb or self._sym_bufs[0].device != srcs[0].device:
+            self._sym_bufs = [torch.zeros(mb * (2 if m else 1), s.shape[1], device=s.device) for m, s in zip(self._sym_modes, srcs)]
+            self._sym_bufs_gather = None
+        key = tuple(s.data_ptr() for s in srcs)
+        if self._sym_bufs_gather is None or self._sym_bufs_gather[0] != key:
+            self._sym_bufs_gather = (key, self._sym_gatherer(srcs, self._sym_bufs))
+        gather, bufs = self._sym_bufs_gather[1], self._sym_bufs
+        indices = torch.randperm(self.num_mini_batches * mb, requires_grad=False, device=self.device)   # RS:63-112: one permutation, reused
+        adaptive = self.desired_kl is not None and self.schedule == "adaptive"
+        sums = torch.zeros(3, device=self.device)        # value loss, surrogate loss, last KL
+        self.num_updates = self.num_learning_epochs * self.num_mini_batches
+        for _ in range(self.num_learning_epochs):
+            for i in range(self.num_mini_batches):
+                gather(indices[i * mb:(i + 1) * mb])
+                if self._device_lr:
+                    self._minibatch_step(bufs, sums)
+                    continue
+                surrogate_loss, value_loss, loss, kl_mean = self._losses_sym(*bufs)
+                if adaptive:
+                    self._apply_kl(kl_mean.item())
+                if not torch.isfinite(loss):
+                    continue
+                self.optimizer.zero_grad()
+                loss.backward()
+                nn.utils.clip_grad_norm_(self.actor_critic.parameters(), self.max_grad_norm)
+                self.optimizer.step()
+                sums[0] += value_loss.detach(); sums[1] += surrogate_loss.detach()
+        host = sums.tolist()
+        if self._device_lr:
+            self.mean_kl = host[2]
+            self.learning_rate = float(self._lr_t.item())
+        return host[0] / self.num_updates, host[1] / self.num_updates
 
     def _update_device(self):
         """Same arithmetic as update(), no host round-trips inside the minibatch loop."""
@@ -570,8 +720,9 @@ class PPO:
         """One PPO minibatch step on static tensors (the arithmetic of _update_device)."""
         obs, cobs, actions, target_values, advantages, returns, old_logp, old_mu, old_sigma = batch
         adaptive = self.desired_kl is not None and self.schedule == "adaptive"
-        surrogate_loss, value_loss, loss, kl_mean = self._losses(obs, cobs, actions, target_values, advantages, returns,
-                                                                  old_logp, old_mu, old_sigma)
+        losses = self._losses if self.symmetry is None else self._losses_sym
+        surrogate_loss, value_loss, loss, kl_mean = losses(obs, cobs, actions, target_values, advantages, returns,
+                                                           old_logp, old_mu, old_sigma)
         # grads dropped, not zero-filled: backward then WRITES each .grad (from the graph's private pool on replay) instead of
         # accumulating into a zeroed one -- one fill and one add kernel less per parameter and step (GRX_PPO_GRAD_NONE=0: fill)
         self.optimizer.zero_grad(set_to_none=os.environ.get("GRX_PPO_GRAD_NONE", "1") != "0")
@@ -650,7 +801,8 @@ class PPO:
         st, dev = self.storage, self.device
         widths = [st.observations.shape[-1], (st.pri_observations if st.pri_observations is not None else st.observations).shape[-1],
                   st.actions.shape[-1], 1, 1, 1, 1, st.mu.shape[-1], st.sigma.shape[-1]]
-        self._static = [torch.zeros(mb, w, device=dev) for w in widths]
+        rows = [mb] * len(widths) if self.symmetry is None else [mb * (2 if m else 1) for m in self._sym_modes]   # (symmetry: the mirrored half behind)
+        self._static = [torch.zeros(r, w, device=dev) for r, w in zip(rows, widths)]
         self._sums = torch.zeros(3, device=dev)
         # warm-up runs real optimizer steps (allocator / lazy-state initialisation): snapshot and restore everything they touch
         ac_state = [p.detach().clone() for p in self.actor_critic.parameters()]   # (not load_state_dict: it rewrites std, AC:116-134)
@@ -736,14 +888,18 @@ class PPO:
         srcs = [flat(x) for x in (st.observations, cobs, st.actions, st.values, st.advantages, st.returns, st.actions_log_prob, st.mu, st.sigma)]
         indices = torch.randperm(self.num_mini_batches * mb, requires_grad=False, device=self.device)   # RS:63-112: one permutation, reused
         self._sums.zero_()
+        if self.symmetry is not None:
+            self._sym_sum.zero_()   # (the dry runs of a capture added to it)
         multi = _collective_path()
         gather = None
         if self._fused_store:   # (libgrx_ppo.so is in use)
             key = tuple(s.data_ptr() for s in srcs) + tuple(b.data_ptr() for b in self._static)
             if getattr(self, "_gather_key", None) != key:
                 from .fused_loss import RowGather
-                self._gather, self._gather_key = RowGather(srcs, self._static), key
+                self._gather, self._gather_key = (RowGather(srcs, self._static) if self.symmetry is None else self._sym_gatherer(srcs, self._static)), key
             gather = self._gather
+        elif self.symmetry is not None:
+            gather = self._sym_gatherer(srcs, self._static)
         for _ in range(self.num_learning_epochs):
             for i in range(self.num_mini_batches):
                 idx = indices[i * mb:(i + 1) * mb]

@@ -80,6 +80,12 @@ class OnPolicyRunner:
         # a recurrent policy: an LSTM in front of the actor's and the critic's MLP.  Not config keys either (`--recurrent` /
         # `--rnn_hidden_size` or assignments to train_cfg.runner.policy_class_name / train_cfg.policy.rnn_hidden_size set them)
         self.recurrent = bool(getattr(policy_cls, "is_recurrent", False))
+        # left-right symmetry: mirrored minibatches and / or a mirror loss in PPO's update; the maps are built here from the env.
+        # Not config keys either (`--symmetry` / `--symmetry_coef` or assignments to train_cfg.algorithm set them); nothing of it is saved
+        self.symmetry = self.algorithm_cfg.get("symmetry") or None
+        self._symmetry_maps = None
+        if self.symmetry is not None:
+            self._check_symmetry()
         if self.recurrent:
             self._check_recurrent()
         if self.distill_from is not None:
@@ -111,7 +117,12 @@ class OnPolicyRunner:
             self._alt_inputs = self._distill_inputs
         else:
             actor_critic = policy_cls(actor_in, critic_in, env.num_actions, **self.policy_cfg).to(device)
-            self.algorithm = _ALGORITHMS[self.cfg["algorithm_class_name"]](actor_critic=actor_critic, device=device, **self.algorithm_cfg)
+            extra = {}
+            if self.symmetry is not None:   # (a model the joint map refuses, an asymmetric height scan: build_maps' ValueError)
+                from .symmetry import build_maps
+                self._symmetry_maps = extra["symmetry_maps"] = build_maps(env, device, self.obs_history_length, self.critic_obs_history_length,
+                                                                           self.privileged_actor)
+            self.algorithm = _ALGORITHMS[self.cfg["algorithm_class_name"]](actor_critic=actor_critic, device=device, **self.algorithm_cfg, **extra)
             if self.privileged_actor:
                 self._alt_inputs = self._privileged_inputs
         self.alg = self.algorithm
@@ -133,6 +144,11 @@ class OnPolicyRunner:
                 self.obs_normalizer = EmpiricalNormalization(actor_in).to(device)   # (history first, then normalisation: the stacked widths)
             if env.num_pri_obs is not None and self.distill_from is None:   # (a distillation run has no critic)
                 self.critic_obs_normalizer = EmpiricalNormalization(critic_in).to(device)
+        if self._symmetry_maps is not None and self.empirical_normalization:   # (the storage holds normalised rows: the maps follow the statistics)
+            actor_norm = self.obs_normalizer if self.obs_normalizer is not None else self.critic_obs_normalizer   # (privileged actor: the critic's)
+            self._symmetry_maps.obs_normalizer = actor_norm
+            self._symmetry_maps.critic_obs_normalizer = self.critic_obs_normalizer if self.critic_obs_normalizer is not None else actor_norm
+            self._symmetry_maps.refresh()
         self._pending_state = None   # what load_train_state() restored and learn() still has to apply
         self._log_buffers = None     # learn()'s running episode reward / length and the finished episodes' deques
         self._next_iteration = None  # the iteration a save() from inside learn() resumes at
@@ -310,6 +326,18 @@ class OnPolicyRunner:
         if self.distill_from is not None:
             raise ValueError("privileged_actor and distill_from exclude each other: the student reads the actor's observations")
 
+    def _check_symmetry(self):
+        """what --symmetry does not combine with"""
+        from .symmetry import MODES
+        if self.symmetry not in MODES:
+            raise ValueError(f"--symmetry must be one of {MODES}, not {self.symmetry!r}")
+        if self.recurrent:
+            raise ValueError("--symmetry and --recurrent exclude each other: a mirrored minibatch of a recurrent policy is not implemented")
+        if self.distill_from is not None:
+            raise ValueError("--symmetry and --distill_from exclude each other: a distillation run has no PPO update to mirror")
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("--symmetry with a world size above 1 is not implemented: it trains in one process only")
+
     def _check_recurrent(self):
         """what a recurrent policy (--recurrent) does not combine with"""
         if self.obs_history_length != 1 or self.critic_obs_history_length != 1:
@@ -369,6 +397,8 @@ class OnPolicyRunner:
             w.add_scalar("Loss/surrogate", locs["mean_surrogate_loss"], it)
             w.add_scalar("Loss/learning_rate", alg.learning_rate, it)
             w.add_scalar("Loss/kl", alg.mean_kl, it)
+            if self.symmetry is not None:
+                w.add_scalar("Loss/symmetry", alg.mean_symmetry_loss, it)
         w.add_scalar("Perf/total_fps", fps, it)
         w.add_scalar("Perf/collection time", locs["collection_time"], it)
         w.add_scalar("Perf/learning_time", locs["learn_time"], it)

@@ -2,6 +2,7 @@
 
     python -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless --num_envs 4096
     python -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless --recurrent --rnn_hidden_size 256     (an LSTM policy: DESIGN.md 4.10)
+    python -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless --symmetry both --symmetry_coef 1.0   (mirrored minibatches + mirror loss: DESIGN.md 4.11)
     torchrun --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless
 """
 import os

@@ -75,6 +75,9 @@ def get_args(argv=None):
     p.add_argument("--recurrent", action="store_true", default=False,
                    help="A recurrent policy: an LSTM in front of the actor's and the critic's MLP (saved in the checkpoint; play needs the same flag)")
     p.add_argument("--rnn_hidden_size", type=int, default=256, help="Hidden size of --recurrent's LSTMs: a multiple of 32 in 32..1024")
+    p.add_argument("--symmetry", type=str, choices=["augment", "loss", "both"],
+                   help="Left-right symmetry in PPO's update: mirrored minibatches (augment), a mirror loss (loss) or both; nothing is saved")
+    p.add_argument("--symmetry_coef", type=float, default=1.0, help="Weight of --symmetry's mirror loss (loss / both; default 1.0)")
     args = p.parse_args(argv)
     if args.obs_history < 1 or args.critic_obs_history < 1:
         raise ValueError(f"--obs_history and --critic_obs_history must be >= 1, got {args.obs_history} and {args.critic_obs_history}")
@@ -125,6 +128,9 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
             cfg_train.runner.distill_loss = args.distill_loss
         if getattr(args, "distill_noise_std", None) is not None:   # (likewise)
             cfg_train.runner.distill_noise_std = float(args.distill_noise_std)
+        if getattr(args, "symmetry", None) is not None:   # (likewise: the algorithm config has no such keys otherwise)
+            cfg_train.algorithm.symmetry = args.symmetry
+            cfg_train.algorithm.symmetry_coef = float(getattr(args, "symmetry_coef", 1.0))
         if getattr(args, "recurrent", False):   # (likewise: the policy config has no rnn_hidden_size otherwise)
             cfg_train.runner.policy_class_name = "ActorCriticRecurrent"
             cfg_train.policy.rnn_hidden_size = int(getattr(args, "rnn_hidden_size", 256))
