@@ -238,6 +238,27 @@ int grx_sym_gather_rows(int n_tensors, const float* const* src, float* const* ds
                         const int* const* perm, const float* const* scale, const float* const* offset, const long long* idx, int mb,
                         void* stream);
 
+/* The intrinsic reward of random network distillation for one rollout step (rsl_rl 2.x `rnd_cfg`; rl/rnd.py): the error of
+ * the trained predictor against the fixed random target, divided by the running spread of its own discounted return, added to the env's
+ * reward.  pred, targ: [N][E] contiguous fp32.  ret [N]: in/out, the per-env discounted return of r.  count (int64) / mean / var / std:
+ * single-element device state of the return's normaliser, EmpiricalNormalization's for one column.  rewards [N]: in/out (the rollout
+ * storage's row of this step).  intrinsic [N]: out.  raw [N]: out, or NULL.  Three launches in stream order:
+ *     1. r[n] = sqrt(sum_e (targ[n][e] - pred[n][e])^2);  ret[n] = fmaf(gamma, ret[n], r[n]);  raw[n] = r[n];  per slab of 128 rows the
+ *        centred triple {n, mean, M2} of the new ret -> partials (the slab's mean is formed before its squares are summed)
+ *     2. grx_obs_norm_merge(slabs, cols = 1): the triples merged in index order, then count += n; rate = n / count; delta = m - mean;
+ *        mean += rate * delta; var += rate * (v - var + delta * (m - mean_new)); std = sqrt(var).  One block; the only writer of the state
+ *     3. x = weight * r[n] / (std + eps) with the std just written;  intrinsic[n] = x;  rewards[n] += x
+ * The power of two >= E (at most 64) lanes share a row: a lane adds the squares of its elements j, j + G, ... in index order, the lanes add
+ * in an xor butterfly -- the order of a row's sum is a function of E alone, so r[n] depends neither on N nor on the other rows; the slab
+ * geometry is a function of N alone.  No atomics: the same inputs give the same bytes.  Between the first and the third launch `intrinsic`
+ * holds r.  rewards, intrinsic, raw, ret must not overlap.  `partials`: 8-byte aligned scratch of grx_rnd_reward_partials_size(N) floats
+ * (0: invalid N).
+ * Returns 0, or negative with nothing launched and nothing written for N < 1, N > 2^24 (a triple carries its n as a float), E outside
+ * 1..256, N * E >= 2^31, a NULL pointer other than raw or a misaligned `partials`; negative for a failed launch. */
+int grx_rnd_reward_partials_size(int N);
+int grx_rnd_reward(int N, int E, const float* pred, const float* targ, float gamma, float weight, float eps, float* ret, long long* count,
+                   float* mean, float* var, float* std, float* rewards, float* intrinsic, float* raw, float* partials, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

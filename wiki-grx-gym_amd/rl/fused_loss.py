@@ -80,6 +80,11 @@ def load_ppo_library():
         pp = C.POINTER(C.c_void_p)
         lib.grx_sym_gather_rows.restype = C.c_int
         lib.grx_sym_gather_rows.argtypes = [C.c_int, pp, pp, C.POINTER(C.c_int), C.POINTER(C.c_int), pp, pp, pp, fp, C.c_int, C.c_void_p]
+        # random network distillation (rl/rnd.py)
+        lib.grx_rnd_reward_partials_size.restype = C.c_int
+        lib.grx_rnd_reward_partials_size.argtypes = [C.c_int]
+        lib.grx_rnd_reward.restype = C.c_int
+        lib.grx_rnd_reward.argtypes = [C.c_int, C.c_int, fp, fp, C.c_float, C.c_float, C.c_float] + [fp] * 9 + [C.c_void_p]
         _LIB = lib
     return _LIB
 

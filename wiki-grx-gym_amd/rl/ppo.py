@@ -137,6 +137,8 @@ class PPO:
         self.symmetry, self._sym, self.symmetry_coef, self.mean_symmetry_loss = None, None, 0, 0.0
         if symmetry is not None:
             self._init_symmetry(symmetry, symmetry_coef, symmetry_maps)
+        # random network distillation (rl/rnd.py): the runner builds it under `--rnd` and assigns it; None runs nothing of it
+        self.rnd = None
         self.num_updates = 0
         self._params = [p for p in self.actor_critic.parameters() if p.requires_grad]
         n = sum(p.numel() for p in self._params)
@@ -339,6 +341,11 @@ class PPO:
         self.storage.add_transitions(t)
         t.clear()
         self.actor_critic.reset(dones)
+
+    def rnd_step(self, frame, step):
+        """after process_env_step of rollout step `step`: the intrinsic reward of the raw frame the env just returned, added to the
+        storage's reward row of that step in place (the row holds the env's reward and the time-out bootstrap by then)"""
+        self.rnd.rollout_step(frame, self.storage.rewards[step], step)
 
     def compute_returns(self, last_critic_obs):
         self._join_critic()

@@ -86,6 +86,14 @@ class OnPolicyRunner:
         self._symmetry_maps = None
         if self.symmetry is not None:
             self._check_symmetry()
+        # random network distillation: an intrinsic reward added to the rollout's reward rows, its networks trained after
+        # PPO's update.  Not config keys either (`--rnd` / `--rnd_*` or assignments to train_cfg.algorithm set them): without `rnd` nothing of
+        # rl/rnd.py is constructed.  The algorithm's own keyword arguments are what is left
+        rnd_cfg = {k[len("rnd_"):]: v for k, v in self.algorithm_cfg.items() if k.startswith("rnd_")} if self.algorithm_cfg.get("rnd") else None
+        self.algorithm_cfg = {k: v for k, v in self.algorithm_cfg.items() if k != "rnd" and not k.startswith("rnd_")}
+        self.rnd = None
+        if rnd_cfg is not None:
+            self._check_rnd(env, rnd_cfg)
         if self.recurrent:
             self._check_recurrent()
         if self.distill_from is not None:
@@ -125,6 +133,12 @@ class OnPolicyRunner:
             self.algorithm = _ALGORITHMS[self.cfg["algorithm_class_name"]](actor_critic=actor_critic, device=device, **self.algorithm_cfg, **extra)
             if self.privileged_actor:
                 self._alt_inputs = self._privileged_inputs
+            if rnd_cfg is not None:   # (after the policy: its initial parameters are those of a run without the flag)
+                from .rnd import RandomNetworkDistillation
+                state = rnd_cfg.get("state", "privileged")
+                self.rnd = self.algorithm.rnd = RandomNetworkDistillation(
+                    env.num_pri_obs if state == "privileged" else env.num_obs, env.num_envs, self.cfg["num_steps_per_env"], device,
+                    **rnd_cfg)
         self.alg = self.algorithm
         self.num_steps_per_env, self.save_interval = self.cfg["num_steps_per_env"], self.cfg["save_interval"]
         # exact resume: every save() also writes train_state_<it>.pt, the whole training state; not a config key
@@ -212,10 +226,14 @@ class OnPolicyRunner:
         tot_iter = self.current_learning_iteration + num_learning_iterations
         for it in range(self.current_learning_iteration, tot_iter):
             start = time.time()
+            if self.rnd is not None:
+                self.rnd.iteration = it
             with torch.inference_mode():
                 for t_ in range(self.num_steps_per_env):
                     actions = alg.act(obs, critic_obs)
                     obs, pri, rewards, dones, infos = env.step(actions)
+                    if self.rnd is not None:   # the raw frame: before history, normalisation and the privileged actor's re-routing
+                        rnd_frame = (pri if self.rnd.state == "privileged" else obs).to(self.device)
                     critic_obs = pri if pri is not None else obs
                     obs, critic_obs, rewards, dones = obs.to(self.device), critic_obs.to(self.device), rewards.to(self.device), dones.to(self.device)
                     if self._alt_inputs is not None:
@@ -232,6 +250,8 @@ class OnPolicyRunner:
                         alg.process_env_step(rewards, dones, infos, log=(cur_rew, cur_len, done_rew[t_], done_len[t_]))
                     else:
                         alg.process_env_step(rewards, dones, infos)
+                    if self.rnd is not None:   # into the storage's reward row of this step; the logged episode rewards stay the env's
+                        alg.rnd_step(rnd_frame, t_)
                 if self.log_dir is not None:   # one device->host transfer per iteration
                     m = alg.storage.dones.squeeze(-1).bool()
                     rewbuffer.extend(done_rew[m].cpu().tolist())
@@ -245,6 +265,10 @@ class OnPolicyRunner:
                 mean_behavior_loss = alg.update()
             else:
                 mean_value_loss, mean_surrogate_loss = alg.update()
+            if self.rnd is not None:   # the predictor's regression on this rollout, with PPO's epoch and minibatch counts
+                mean_rnd_loss = self.rnd.update(alg.num_learning_epochs, alg.num_mini_batches)
+                if self.log_dir is not None and self.is_main:
+                    mean_intrinsic_reward = self.rnd.intrinsic.mean().item()
             alg.clear_storage()
             if self.sync_timers:
                 torch.cuda.synchronize()
@@ -338,6 +362,21 @@ class OnPolicyRunner:
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise NotImplementedError("--symmetry with a world size above 1 is not implemented: it trains in one process only")
 
+    def _check_rnd(self, env, rnd_cfg):
+        """what --rnd does not combine with"""
+        from .rnd import STATES
+        state = rnd_cfg.get("state", "privileged")
+        if state not in STATES:
+            raise ValueError(f"--rnd_state must be one of {STATES}, not {state!r}")
+        if state == "privileged" and env.num_pri_obs is None:
+            raise ValueError("--rnd_state privileged: this env has no privileged observations (pass --rnd_state obs)")
+        if self.distill_from is not None:
+            raise ValueError("--rnd and --distill_from exclude each other: a distillation run has no reward for an intrinsic one to add to")
+        if bool(self.cfg.get("exact_resume", False)):
+            raise NotImplementedError("--rnd with --exact_resume: RND's state is not part of train_state_<it>.pt")
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("--rnd with a world size above 1 is not implemented: the return statistics are per process")
+
     def _check_recurrent(self):
         """what a recurrent policy (--recurrent) does not combine with"""
         if self.obs_history_length != 1 or self.critic_obs_history_length != 1:
@@ -399,6 +438,10 @@ class OnPolicyRunner:
             w.add_scalar("Loss/kl", alg.mean_kl, it)
             if self.symmetry is not None:
                 w.add_scalar("Loss/symmetry", alg.mean_symmetry_loss, it)
+            if self.rnd is not None:
+                w.add_scalar("Loss/rnd", locs["mean_rnd_loss"], it)
+                w.add_scalar("Train/mean_intrinsic_reward", locs["mean_intrinsic_reward"], it)
+                w.add_scalar("Train/rnd_weight", self.rnd.weight(it), it)
         w.add_scalar("Perf/total_fps", fps, it)
         w.add_scalar("Perf/collection time", locs["collection_time"], it)
         w.add_scalar("Perf/learning_time", locs["learn_time"], it)
@@ -442,6 +485,8 @@ class OnPolicyRunner:
             saved["distillation"] = dict(self.distillation)
         if self.recurrent:   # (likewise)
             saved["recurrent"] = {"hidden_size": self.algorithm.actor_critic.rnn_hidden_size}
+        if self.rnd is not None:   # (likewise): both networks, RND's normaliser, the discounted-return state, the optimizer, the configuration
+            saved["rnd"] = self.rnd.checkpoint()
         torch.save(saved, path)
         if self.exact_resume:
             torch.save(self._train_state(), train_state_path(path))
@@ -537,6 +582,12 @@ class OnPolicyRunner:
         self.algorithm.invalidate_graphs()
         if load_optimizer:
             self.algorithm.load_optimizer_state(loaded["optimizer_state_dict"])
+        if self.rnd is not None and "rnd" in loaded:
+            self.rnd.load_checkpoint(loaded["rnd"], load_optimizer)
+        elif self.rnd is not None:
+            print(f"{path} holds no rnd entry: random network distillation starts fresh")
+        elif "rnd" in loaded:
+            print(f"{path} holds an rnd entry, this runner has no --rnd: ignored")
         self.current_learning_iteration = loaded["iter"]
         return loaded["infos"]
 

@@ -78,6 +78,20 @@ def get_args(argv=None):
     p.add_argument("--symmetry", type=str, choices=["augment", "loss", "both"],
                    help="Left-right symmetry in PPO's update: mirrored minibatches (augment), a mirror loss (loss) or both; nothing is saved")
     p.add_argument("--symmetry_coef", type=float, default=1.0, help="Weight of --symmetry's mirror loss (loss / both; default 1.0)")
+    p.add_argument("--rnd", action="store_true", default=False,
+                   help="Random network distillation: an intrinsic reward (predictor error against a fixed random network) added to the env's")
+    p.add_argument("--rnd_weight", type=float, default=0.1, help="Weight of --rnd's intrinsic reward (default 0.1, not tuned)")
+    p.add_argument("--rnd_weight_schedule", type=str, choices=["constant", "linear", "step"], default="constant",
+                   help="--rnd_weight over the PPO iterations: constant, linear (--rnd_final_weight from --rnd_start_it to --rnd_end_it) or "
+                        "step (--rnd_final_weight from --rnd_at_it on)")
+    p.add_argument("--rnd_final_weight", type=float, help="The weight a linear / step schedule ends at (default: --rnd_weight)")
+    p.add_argument("--rnd_start_it", type=int, default=0, help="First iteration of a linear schedule's ramp")
+    p.add_argument("--rnd_end_it", type=int, default=0, help="Last iteration of a linear schedule's ramp")
+    p.add_argument("--rnd_at_it", type=int, default=0, help="Iteration at which a step schedule switches")
+    p.add_argument("--rnd_state", type=str, choices=["privileged", "obs"], default="privileged",
+                   help="The frame --rnd's networks read: the env's privileged frame (no observation noise) or the actor's raw frame")
+    p.add_argument("--rnd_num_outputs", type=int, default=32, help="Width of --rnd's embedding (1..256)")
+    p.add_argument("--rnd_learning_rate", type=float, default=1e-3, help="Learning rate of --rnd's predictor (fixed)")
     args = p.parse_args(argv)
     if args.obs_history < 1 or args.critic_obs_history < 1:
         raise ValueError(f"--obs_history and --critic_obs_history must be >= 1, got {args.obs_history} and {args.critic_obs_history}")
@@ -131,6 +145,15 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
         if getattr(args, "symmetry", None) is not None:   # (likewise: the algorithm config has no such keys otherwise)
             cfg_train.algorithm.symmetry = args.symmetry
             cfg_train.algorithm.symmetry_coef = float(getattr(args, "symmetry_coef", 1.0))
+        if getattr(args, "rnd", False):   # (likewise; the --rnd_* values travel only with --rnd)
+            a = cfg_train.algorithm
+            a.rnd = True
+            a.rnd_weight, a.rnd_weight_schedule = float(getattr(args, "rnd_weight", 0.1)), getattr(args, "rnd_weight_schedule", "constant")
+            fw = getattr(args, "rnd_final_weight", None)
+            a.rnd_final_weight = None if fw is None else float(fw)
+            a.rnd_start_it, a.rnd_end_it, a.rnd_at_it = (int(getattr(args, k, 0)) for k in ("rnd_start_it", "rnd_end_it", "rnd_at_it"))
+            a.rnd_state, a.rnd_num_outputs = getattr(args, "rnd_state", "privileged"), int(getattr(args, "rnd_num_outputs", 32))
+            a.rnd_learning_rate = float(getattr(args, "rnd_learning_rate", 1e-3))
         if getattr(args, "recurrent", False):   # (likewise: the policy config has no rnn_hidden_size otherwise)
             cfg_train.runner.policy_class_name = "ActorCriticRecurrent"
             cfg_train.policy.rnn_hidden_size = int(getattr(args, "rnn_hidden_size", 256))
