@@ -262,4 +262,8 @@ int grx_rnd_reward(int N, int E, const float* pred, const float* targ, float gam
 #ifdef __cplusplus
 }
 #endif
+
+/* ... and a state-dependent action noise: the loss and the policy head for an actor whose output layer is [mean | s],
+ * csrc/grx_ppo_noise.hip in the same library */
+#include "grx_ppo_noise.h"
 #endif

@@ -163,6 +163,9 @@ def read_teacher(loaded, path, num_obs, num_pri_obs, num_actions):
     that stream's history length, frame width and frozen normaliser statistics (or None), the actor's hidden sizes (from the shapes of
     actor.model.*.weight) and its tensors.  ValueError when the actor's first layer does not fit history x frame width."""
     sd = loaded["model_state_dict"]
+    if bool((loaded.get("noise") or {}).get("state_dependent", False)):
+        raise ValueError(f"{path} was trained with --state_dependent_std: --distill_from and --state_dependent_std exclude each other, a "
+                         "teacher whose output layer is [mean | s] is not implemented")
     layers = sorted((int(k.split(".")[2]), k) for k in sd if k.startswith("actor.model.") and k.endswith(".weight"))
     if not layers:
         raise ValueError(f"{path} holds no actor (no actor.model.*.weight in its model_state_dict)")

@@ -85,6 +85,13 @@ def load_ppo_library():
         lib.grx_rnd_reward_partials_size.argtypes = [C.c_int]
         lib.grx_rnd_reward.restype = C.c_int
         lib.grx_rnd_reward.argtypes = [C.c_int, C.c_int, fp, fp, C.c_float, C.c_float, C.c_float] + [fp] * 9 + [C.c_void_p]
+        # a state-dependent action noise (rl/modules.py state_dependent_std)
+        lib.grx_ppo_loss_sd_partials_size.restype = C.c_int
+        lib.grx_ppo_loss_sd_partials_size.argtypes = [C.c_int]
+        lib.grx_ppo_loss_sd.restype = C.c_int
+        lib.grx_ppo_loss_sd.argtypes = [C.c_int, C.c_int, fp, C.c_int] + [fp] * 8 + [C.c_float, C.c_float, C.c_float, C.c_int] + [fp] * 4 + [C.c_void_p]
+        lib.grx_mlp_policy_head_sd.restype = C.c_int
+        lib.grx_mlp_policy_head_sd.argtypes = [C.c_int] * 3 + [fp] * 3 + [C.c_int] + [fp] * 5 + [C.c_void_p]
         _LIB = lib
     return _LIB
 
@@ -208,6 +215,48 @@ def fused_ppo_loss(mu, std, value, actions, old_logp, old_mu, old_sigma, advanta
                    clip_param, value_loss_coef, entropy_coef, use_clipped_value_loss):
     return FusedPPOLoss.apply(mu, std, value, actions, old_logp, old_mu, old_sigma, advantages, returns, target_values,
                               clip_param, value_loss_coef, entropy_coef, use_clipped_value_loss)
+
+
+class FusedPPOLossSD(torch.autograd.Function):
+    """FusedPPOLoss for a state-dependent sigma (grx_ppo_loss_sd): (raw [B, 2A] = [mean | s], value [B] or [B, 1]; data...) -> tensor
+    [surrogate, value_loss, total_loss, mean_kl].  The kernel writes the gradient onto the actor's raw output: no split, cat or
+    exp-backward launches around it."""
+
+    @staticmethod
+    def forward(ctx, raw, value, actions, old_logp, old_mu, old_sigma, advantages, returns, target_values,
+                log_std, clip_param, value_loss_coef, entropy_coef, use_clipped_value_loss):
+        lib = load_ppo_library()
+        B, A = actions.shape
+        if tuple(raw.shape) != (B, 2 * A):
+            raise RuntimeError(f"fused_ppo_loss_sd: raw is {tuple(raw.shape)}, expected {(B, 2 * A)} ([mean | s] of {A} actions)")
+        raw_c, value_c = _f32c(raw), _f32c(value).reshape(-1)
+        data = [_f32c(t) for t in (actions, old_logp, old_mu, old_sigma, advantages, returns, target_values)]
+        out = torch.empty(4, device=raw.device, dtype=torch.float32)
+        d_raw = torch.empty_like(raw_c)
+        d_value = torch.empty_like(value_c)
+        partials = torch.empty(lib.grx_ppo_loss_sd_partials_size(B), device=raw.device, dtype=torch.float32)
+        stream = torch.cuda.current_stream(raw.device).cuda_stream
+        with torch.cuda.device(raw.device):
+            rc = lib.grx_ppo_loss_sd(B, A, raw_c.data_ptr(), int(bool(log_std)), value_c.data_ptr(), *[t.data_ptr() for t in data],
+                                     float(clip_param), float(value_loss_coef), float(entropy_coef), int(bool(use_clipped_value_loss)),
+                                     out.data_ptr(), d_raw.data_ptr(), d_value.data_ptr(), partials.data_ptr(), C.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError(f"grx_ppo_loss_sd failed ({rc}): batch {B}, num_actions {A}")
+        ctx.save_for_backward(d_raw, d_value)
+        ctx.value_shape = value.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        d_raw, d_value = ctx.saved_tensors
+        gl = g[2]   # only the total loss is differentiable
+        return (d_raw * gl, (d_value * gl).reshape(ctx.value_shape)) + (None,) * 12
+
+
+def fused_ppo_loss_sd(raw, value, actions, old_logp, old_mu, old_sigma, advantages, returns, target_values,
+                      log_std, clip_param, value_loss_coef, entropy_coef, use_clipped_value_loss):
+    return FusedPPOLossSD.apply(raw, value, actions, old_logp, old_mu, old_sigma, advantages, returns, target_values,
+                                log_std, clip_param, value_loss_coef, entropy_coef, use_clipped_value_loss)
 
 
 def colsum(x):
@@ -356,9 +405,10 @@ def mlp_forward(mlp, x):
     return x
 
 
-def policy_act(mlp, std, x, eps):
+def policy_act(mlp, std, x, eps, state_dependent=None):
     """actor forward + sample + log-prob: (actions, logp [M], mu, sigma) -- the hidden layers as in mlp_forward, the output
-    layer fused with `mu + std * eps` and Normal.log_prob summed over the actions."""
+    layer fused with `mu + std * eps` and Normal.log_prob summed over the actions.  state_dependent "scalar" / "log": the output
+    layer is [mean | s] (2A rows) and sigma = s or exp(s) per row (grx_mlp_policy_head_sd, still one launch); `std` is not read."""
     lib = load_ppo_library()
     lin = _linears_of(mlp)
     bf16 = _bf16_hidden(mlp)
@@ -368,9 +418,16 @@ def policy_act(mlp, std, x, eps):
         for w, b in lin[:-1]:
             x = _layer(lib, x, w, b, True, stream, bf16)
         w, b = lin[-1]
-        M, A = x.shape[0], w.shape[0]
+        M, A = x.shape[0], w.shape[0] // (2 if state_dependent is not None else 1)
         actions, mu, sigma = (torch.empty(M, A, device=x.device, dtype=torch.float32) for _ in range(3))
         logp = torch.empty(M, device=x.device, dtype=torch.float32)
+        if state_dependent is not None:
+            rc = lib.grx_mlp_policy_head_sd(M, x.shape[1], A, x.data_ptr(), _f32c(w).data_ptr(), b.data_ptr() if b is not None else None,
+                                            int(state_dependent == "log"), _f32c(eps).data_ptr(), actions.data_ptr(), logp.data_ptr(),
+                                            mu.data_ptr(), sigma.data_ptr(), stream)
+            if rc:
+                raise RuntimeError(f"grx_mlp_policy_head_sd failed ({rc})")
+            return actions, logp, mu, sigma
         rc = lib.grx_mlp_policy_head(M, x.shape[1], A, x.data_ptr(), w.data_ptr(), b.data_ptr() if b is not None else None,
                                      _f32c(std).data_ptr(), _f32c(eps).data_ptr(), actions.data_ptr(), logp.data_ptr(),
                                      mu.data_ptr(), sigma.data_ptr(), stream)

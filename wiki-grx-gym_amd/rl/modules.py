@@ -6,7 +6,8 @@ rsl_rl/modules/actor_critic_mlp.py:10-231, mlp.py:7-42): separate actor / critic
 State-dict layout (``actor.model.<i>.weight`` ..., ``critic.model.<i>...``, ``std``) equals the
 reference's so checkpoints (``model_<it>.pt``) interchange; ``load_state_dict`` reproduces the
 reference quirk of overwriting ``std`` with ``set_noise_std`` unless ``set_std=False``
-(actor_critic_mlp.py:116-134)."""
+(actor_critic_mlp.py:116-134).  Opt-in: ``noise_std_type="log"`` holds ``log_std`` instead of ``std``,
+``state_dependent_std=True`` no noise parameter at all -- the actor's output layer is ``[mean | s]``."""
 import torch
 import torch.nn as nn
 from torch.distributions import Normal
@@ -173,34 +174,113 @@ class MLP(nn.Module):
         return self.model(x)
 
 
+NOISE_STD_TYPES = ("scalar", "log")   # ActorCriticMLP(noise_std_type=...): sigma is the parameter, or exp of it
+
+
+class MeanHead(nn.Module):
+    """the first `num_actions` outputs of an actor whose output layer is [mean | s] (state_dependent_std): what inference, play and
+    the exported TorchScript module act on"""
+
+    def __init__(self, actor, num_actions: int):
+        super().__init__()
+        self.actor, self.num_actions = actor, int(num_actions)
+
+    def forward(self, x):
+        return torch.narrow(self.actor(x), -1, 0, self.num_actions)
+
+
 class ActorCriticMLP(nn.Module):
+    """Two options for the exploration noise, both off by default:
+
+    * noise_std_type="log" (rsl_rl 2.x): the module holds `log_std` instead of `std`, sigma = exp(log_std) -- it cannot reach zero.
+    * state_dependent_std=True (rsl_rl 3.x): no noise parameter; the actor's output layer has 2A outputs [mean | s] and sigma = s
+      ("scalar") or exp(s) ("log") per state.  The s rows start at zero weight and a bias of init_noise_std resp. log(init_noise_std + 1e-7).
+
+    `noise_std()` is the differentiable [A] sigma of the first three parametrisations; every reader goes through it."""
+
     def __init__(self, actor_num_input, critic_num_input, actor_num_output, actor_hidden_dims=(256, 256, 256),
                  critic_hidden_dims=(256, 256, 256), activation="elu", fixed_std=False, init_noise_std=1.0,
-                 set_std=True, set_noise_std=1.0, actor_output_activation=None, critic_output_activation=None, actor_output_gain=1.0, **kwargs):
+                 set_std=True, set_noise_std=1.0, actor_output_activation=None, critic_output_activation=None, actor_output_gain=1.0,
+                 noise_std_type="scalar", state_dependent_std=False, **kwargs):
         if kwargs:
             print("ActorCritic.__init__ got unexpected arguments, which will be ignored: " + str(list(kwargs)))
+        if noise_std_type not in NOISE_STD_TYPES:
+            raise ValueError(f"noise_std_type must be one of {NOISE_STD_TYPES}, not {noise_std_type!r}")
+        state_dependent_std = bool(state_dependent_std)
+        if state_dependent_std and actor_output_activation is not None:
+            raise ValueError(f"state_dependent_std with actor_output_activation={actor_output_activation!r}: the output layer is [mean | s], "
+                             "an activation on it is not defined")
+        if state_dependent_std and fixed_std:
+            raise ValueError("state_dependent_std with fixed_std: the actor emits its own sigma, there is no parameter to fix")
         super().__init__()
+        self.noise_std_type, self.state_dependent_std = noise_std_type, state_dependent_std
         self.num_actor_input, self.num_actor_output = actor_num_input, actor_num_output
         self.num_critic_input, self.num_critic_output = critic_num_input, 1
-        self.actor = MLP(actor_num_input, actor_num_output, actor_hidden_dims, activation)
+        self.actor = MLP(actor_num_input, 2 * actor_num_output if state_dependent_std else actor_num_output, actor_hidden_dims, activation)
         self.critic = MLP(critic_num_input, 1, critic_hidden_dims, activation)
+        A = actor_num_output
+        init = torch.as_tensor(init_noise_std, dtype=torch.float32) * torch.ones(A)
+        last = [m for m in self.actor.model if isinstance(m, nn.Linear)][-1]
         if actor_output_gain != 1.0:   # (not in the reference, whose layers keep PyTorch's default init: 1.0.  The build-defined 32-DOF task starts its
             with torch.no_grad():      #  policy near the zero action -- the PD targets' default pose --: envs/config.py GR1T1FullBodyCfgPPO)
-                last = [m for m in self.actor.model if isinstance(m, nn.Linear)][-1]
-                last.weight.mul_(float(actor_output_gain)); last.bias.mul_(float(actor_output_gain))
+                last.weight[:A].mul_(float(actor_output_gain)); last.bias[:A].mul_(float(actor_output_gain))   # (the mean rows: all of them without state_dependent_std)
+        if state_dependent_std:   # rsl_rl 3.x: sigma starts at init_noise_std in every state
+            with torch.no_grad():
+                last.weight[A:].zero_()
+                last.bias[A:].copy_(torch.log(init + 1e-7) if noise_std_type == "log" else init)
         self.fixed_std, self.init_noise_std = fixed_std, init_noise_std
         # (a number, as in the reference -- actor_critic_mlp.py -- or one value per action: the 32-DOF task starts its upper-body joints quieter)
-        self.std = nn.Parameter(torch.as_tensor(init_noise_std, dtype=torch.float32) * torch.ones(actor_num_output))
+        if not state_dependent_std and noise_std_type == "log":
+            self.log_std = nn.Parameter(torch.log(init))
+        elif not state_dependent_std:
+            self.std = nn.Parameter(init.clone())
         # (a scalar or one value per action -- GR1T1FullBodyCfgPPO --: a buffer, so that the fixed_std paths see a tensor on the module's device)
-        self.register_buffer("init_std", torch.as_tensor(init_noise_std, dtype=torch.float32) * torch.ones(actor_num_output), persistent=False)
+        self.register_buffer("init_std", init.clone(), persistent=False)
         self.set_std, self.set_noise_std = set_std, set_noise_std
         self.distribution = None
         Normal.set_default_validate_args = False
 
     is_recurrent = False
 
+    def noise_std(self):
+        """the [A] sigma as the loss differentiates it: `std`, exp(`log_std`), or the init_noise_std buffer under fixed_std"""
+        if self.state_dependent_std:
+            raise RuntimeError("state_dependent_std: sigma is a function of the state (the actor's second output half), there is no [A] sigma")
+        if self.fixed_std:
+            return self.init_std
+        return torch.exp(self.log_std) if self.noise_std_type == "log" else self.std
+
+    def split_raw(self, raw):
+        """(mean, sigma) of a state-dependent actor's raw output [..., 2A]"""
+        A = self.num_actor_output
+        s = raw[..., A:]
+        return raw[..., :A], (torch.exp(s) if self.noise_std_type == "log" else s)
+
+    def inference_actor(self):
+        """the module whose output is the mean action: `actor`, or its first A outputs under state_dependent_std"""
+        return MeanHead(self.actor, self.num_actor_output) if self.state_dependent_std else self.actor
+
+    def assign_noise_std(self, std):
+        """sigma := std [A] in place, whichever parameter holds it (a distilled student's fixed noise into an ordinary policy)"""
+        if self.state_dependent_std:
+            raise RuntimeError("state_dependent_std: there is no noise parameter to set")
+        with torch.no_grad():
+            if self.noise_std_type == "log":
+                self.log_std.copy_(torch.log(std))
+            else:
+                self.std.copy_(std)
+
     def load_state_dict(self, state_dict, strict=True):
         state_dict = dict(state_dict)
+        if self.state_dependent_std:   # (no noise parameter: nothing to overwrite)
+            return super().load_state_dict(state_dict, strict)
+        if self.noise_std_type == "log":   # (the reference's set_std / set_noise_std overwrite belongs to `std`: a log_std loads as saved)
+            if self.fixed_std:
+                with torch.no_grad():
+                    self.log_std.copy_(torch.log(torch.as_tensor(self.init_noise_std, dtype=torch.float32) * torch.ones_like(self.log_std)))
+                self.log_std.requires_grad = False
+                state_dict["log_std"] = self.log_std.detach().clone()
+            return super().load_state_dict(state_dict, strict)
         if self.set_std:
             state_dict["std"] = torch.ones_like(state_dict["std"]) * self.set_noise_std
         # (the reference rebinds self.std.data here, actor_critic_mlp.py:116-134; copying IN PLACE gives the same values and keeps
@@ -236,8 +316,12 @@ class ActorCriticMLP(nn.Module):
         return self.distribution.entropy().sum(dim=-1)
 
     def update_distribution(self, observations):
+        if self.state_dependent_std:
+            mean, std = self.split_raw(self.actor(observations))
+            self.distribution = Normal(mean, std)
+            return
         mean = self.actor(observations)
-        std = self.init_std.to(mean.device) if self.fixed_std else self.std.to(mean.device)
+        std = self.noise_std().to(mean.device)
         self.distribution = Normal(mean, mean * 0.0 + std)
 
     def act(self, observations, **_):
@@ -248,6 +332,8 @@ class ActorCriticMLP(nn.Module):
         return self.distribution.log_prob(actions).sum(dim=-1)
 
     def act_inference(self, observations):
+        if self.state_dependent_std:
+            return self.actor(observations)[..., :self.num_actor_output]
         return self.actor(observations)
 
     def evaluate(self, critic_observations=None, **_):

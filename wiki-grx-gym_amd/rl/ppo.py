@@ -12,7 +12,7 @@ import os
 
 import torch
 import torch.distributed as dist
-from .fused_loss import fused_ppo_loss, mlp_can_fuse, mlp_forward, policy_act
+from .fused_loss import fused_ppo_loss, fused_ppo_loss_sd, mlp_can_fuse, mlp_forward, policy_act
 import torch.nn as nn
 import torch.optim as optim
 
@@ -31,6 +31,11 @@ def _capture_mode():
     default "global" capture mode that call from ANOTHER thread invalidates a capture in progress and takes the process
     down.  "thread_local" confines the legality check to the capturing thread."""
     return "thread_local" if dist.is_available() and dist.is_initialized() else "global"
+
+
+def _noise_std(ac):
+    """the differentiable [A] sigma of a policy: ActorCriticMLP.noise_std() (`std`, or exp(`log_std`)); a policy class without the accessor holds `std`"""
+    return ac.noise_std() if hasattr(ac, "noise_std") else ac.std
 
 
 def _world():
@@ -115,6 +120,19 @@ class PPO:
         self._aux_stream = None
         # a recurrent policy (rl/recurrent.py): the rollout's policy step and the minibatch step run eagerly, nothing is captured
         self._recurrent = bool(getattr(actor_critic, "is_recurrent", False))
+        # a state-dependent action noise (rl/modules.py): the actor's output is [mean | s], the loss and the rollout's head
+        # take it in that form (grx_ppo_loss_sd, grx_mlp_policy_head_sd); captured as the default is
+        self._state_dependent = bool(getattr(actor_critic, "state_dependent_std", False))
+        if self._state_dependent:
+            if self._recurrent:
+                raise ValueError("PPO: --state_dependent_std and --recurrent exclude each other: a recurrent policy with a state-dependent "
+                                 "sigma is not implemented")
+            if symmetry is not None:
+                raise ValueError("PPO: --state_dependent_std and --symmetry exclude each other: a mirror map of the [mean | s] output is "
+                                 "not implemented")
+            if _world() > 1:
+                raise NotImplementedError("PPO: --state_dependent_std with a world size above 1 is not implemented: it trains in one "
+                                          "process only")
         if self._recurrent:
             if _world() > 1:
                 raise NotImplementedError("PPO: a recurrent policy trains in one process only")
@@ -251,7 +269,9 @@ class PPO:
                     if fuse:
                         eps = torch.randn(self._act_in[0].shape[0], ac.num_actor_output, device=self.device)
                         # (fixed_std: update_distribution -- and so the update's log-prob -- uses init_noise_std, not the parameter)
-                        std = ac.init_std.to(ac.std.device).clone() if getattr(ac, "fixed_std", False) else ac.std.detach()
+                        if getattr(ac, "state_dependent_std", False):   # (the output layer is [mean | s]: sigma per row, still one head launch)
+                            return policy_act(ac.actor, None, self._act_in[0], eps, state_dependent=ac.noise_std_type)
+                        std = ac.init_std.clone() if getattr(ac, "fixed_std", False) else _noise_std(ac).detach()
                         return policy_act(ac.actor, std, self._act_in[0], eps)
                     ac.update_distribution(self._act_in[0])   # Normal.sample() checks std >= 0 on the host: not capturable
                     actions = (ac.action_mean + ac.action_std * torch.randn_like(ac.action_mean)).detach()
@@ -524,8 +544,10 @@ class PPO:
         return self._fused_loss and not ac.fixed_std and ac.num_actor_output <= 32   # the kernel's action-count limit
 
     def _forward(self, obs, cobs):
-        """(mu, value): the actor's and the critic's forward of one minibatch"""
+        """(mu, value): the actor's and the critic's forward of one minibatch (state_dependent_std: mu is the actor's raw [mean | s])"""
         ac = self.actor_critic
+        if self._state_dependent and not self._loss_is_fused():
+            return ac.actor(obs), ac.evaluate(cobs)   # (the raw output [mean | s]: _loss_terms splits it)
         if not self._loss_is_fused():
             ac.update_distribution(obs)   # (the torch spelling in _loss_terms reads sigma from the distribution)
             return ac.action_mean, ac.evaluate(cobs)
@@ -552,12 +574,21 @@ class PPO:
         (symmetry "loss": the mirrored rows behind them have no PPO loss)"""
         ac = self.actor_critic
         adaptive = self.desired_kl is not None and self.schedule == "adaptive"
+        if self._state_dependent and self._loss_is_fused():   # (mu is the raw [mean | s]: the gradient lands on it in one launch)
+            out = fused_ppo_loss_sd(mu, value, actions, old_logp, old_mu, old_sigma, advantages, returns, target_values,
+                                    ac.noise_std_type == "log", self.clip_param, self.value_loss_coef, self.entropy_coef,
+                                    self.use_clipped_value_loss)
+            kl_mean = out[3].detach() if adaptive else torch.zeros((), device=self.device)
+            return out[0], out[1], out[2], kl_mean
         if self._loss_is_fused():
-            out = fused_ppo_loss(mu, ac.std, value, actions, old_logp, old_mu, old_sigma, advantages, returns, target_values,
+            out = fused_ppo_loss(mu, _noise_std(ac), value, actions, old_logp, old_mu, old_sigma, advantages, returns, target_values,
                                  self.clip_param, self.value_loss_coef, self.entropy_coef, self.use_clipped_value_loss)
             kl_mean = out[3].detach() if adaptive else torch.zeros((), device=self.device)
             return out[0], out[1], out[2], kl_mean
-        sigma = ac.action_std[:mu.shape[0]]
+        if self._state_dependent:
+            mu, sigma = ac.split_raw(mu)
+        else:
+            sigma = ac.action_std[:mu.shape[0]]
         dist_ = torch.distributions.Normal(mu, sigma, validate_args=False)
         logp, entropy = dist_.log_prob(actions).sum(dim=-1), dist_.entropy().sum(dim=-1)
         kl_mean = torch.zeros((), device=self.device)

@@ -399,7 +399,7 @@ class ActorCriticRecurrent(ActorCriticMLP):
         if fa.is_cuda and self.num_actor_output <= 32 and self.actor.fusable(fa) and self.critic.fusable(fc):
             from .fused_loss import mlp_forward, policy_act
             eps = torch.randn(fa.shape[0], self.num_actor_output, device=fa.device)
-            std = self.init_std if self.fixed_std else self.std.detach()
+            std = self.noise_std().detach()
             actions, logp, mu, sigma = policy_act(self.actor, std, fa, eps)
             return actions, mlp_forward(self.critic, fc), logp, mu, sigma
         with self.on_features():

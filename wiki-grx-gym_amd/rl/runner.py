@@ -94,6 +94,14 @@ class OnPolicyRunner:
         self.rnd = None
         if rnd_cfg is not None:
             self._check_rnd(env, rnd_cfg)
+        # the action noise's parametrisation: `log` holds log_std, `state_dependent_std` lets the actor emit sigma per state.
+        # Not config keys either (`--noise_std_type` / `--state_dependent_std` or assignments to train_cfg.policy set them)
+        self.noise_std_type = self.policy_cfg.get("noise_std_type", "scalar")
+        self.state_dependent_std = bool(self.policy_cfg.get("state_dependent_std", False))
+        self.noise = None   # the "noise" entry of a checkpoint of this run: only when an option is not the default
+        if self.noise_std_type != "scalar" or self.state_dependent_std:
+            self._check_noise()
+            self.noise = {"std_type": self.noise_std_type, "state_dependent": self.state_dependent_std}
         if self.recurrent:
             self._check_recurrent()
         if self.distill_from is not None:
@@ -377,6 +385,25 @@ class OnPolicyRunner:
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise NotImplementedError("--rnd with a world size above 1 is not implemented: the return statistics are per process")
 
+    def _check_noise(self):
+        """what --noise_std_type log / --state_dependent_std do not combine with"""
+        from .modules import NOISE_STD_TYPES
+        if self.noise_std_type not in NOISE_STD_TYPES:
+            raise ValueError(f"--noise_std_type must be one of {NOISE_STD_TYPES}, not {self.noise_std_type!r}")
+        if self.distill_from is not None:
+            which = "--state_dependent_std" if self.state_dependent_std else f"--noise_std_type {self.noise_std_type}"
+            raise ValueError(f"{which} and --distill_from exclude each other: the student's action noise is a fixed buffer "
+                             "(--distill_noise_std), there is no noise parameter to shape")
+        if not self.state_dependent_std:
+            return   # (`log` alone composes with everything the default composes with: only the parameter differs)
+        if self.recurrent:
+            raise ValueError("--state_dependent_std and --recurrent exclude each other: a recurrent policy with a state-dependent sigma is "
+                             "not implemented")
+        if self.symmetry is not None:
+            raise ValueError("--state_dependent_std and --symmetry exclude each other: a mirror map of the [mean | s] output is not implemented")
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("--state_dependent_std with a world size above 1 is not implemented: it trains in one process only")
+
     def _check_recurrent(self):
         """what a recurrent policy (--recurrent) does not combine with"""
         if self.obs_history_length != 1 or self.critic_obs_history_length != 1:
@@ -451,7 +478,12 @@ class OnPolicyRunner:
             w.add_scalar("Train/mean_episode_length", ml, it)
             w.add_scalar("Train/mean_reward/time", mr, self.tot_time)
             w.add_scalar("Train/mean_episode_length/time", ml, self.tot_time)
-        stds = alg.actor_critic.std.detach()
+        if self.state_dependent_std:   # per action, the mean over the rollout just trained on (clear_storage() keeps the rows)
+            stds = alg.storage.sigma.detach().flatten(0, 1).mean(0)
+        elif self.distillation is not None:   # (a student's noise is a fixed buffer)
+            stds = alg.actor_critic.std.detach()
+        else:
+            stds = alg.actor_critic.noise_std().detach()
         for i, s in enumerate(stds):
             w.add_scalar(f"Policy/noise_std_{i}", s.item(), it)
         w.add_scalar("Policy/mean_noise_std", stds.mean().item(), it)
@@ -485,6 +517,8 @@ class OnPolicyRunner:
             saved["distillation"] = dict(self.distillation)
         if self.recurrent:   # (likewise)
             saved["recurrent"] = {"hidden_size": self.algorithm.actor_critic.rnn_hidden_size}
+        if self.noise is not None:   # (likewise)
+            saved["noise"] = dict(self.noise)
         if self.rnd is not None:   # (likewise): both networks, RND's normaliser, the discounted-return state, the optimizer, the configuration
             saved["rnd"] = self.rnd.checkpoint()
         torch.save(saved, path)
@@ -563,6 +597,12 @@ class OnPolicyRunner:
             raise ValueError(f"{path} was saved with recurrent={loaded.get('recurrent')}, this runner has recurrent={mine}: the policy would not "
                              "be the one that was trained (pass --recurrent --rnn_hidden_size H, or set train_cfg.runner.policy_class_name / "
                              "train_cfg.policy.rnn_hidden_size, to match the checkpoint)")
+        if loaded.get("noise") != self.noise:
+            want = loaded.get("noise") or {"std_type": "scalar", "state_dependent": False}
+            raise ValueError(f"{path} was saved with noise={loaded.get('noise')}, this runner has noise={self.noise}: the policy would not be "
+                             f"the one that was trained (pass --noise_std_type {want['std_type']}"
+                             f"{' --state_dependent_std' if want['state_dependent'] else ' without --state_dependent_std'}, or set "
+                             "train_cfg.policy.noise_std_type / train_cfg.policy.state_dependent_std, to match the checkpoint)")
         saved_hist = loaded.get("obs_history", {"actor": 1, "critic": 1})   # (a checkpoint without the key: no history)
         if "distillation" in loaded and self.distillation is None:
             return self._load_student(path, loaded, saved_hist)
@@ -618,13 +658,17 @@ class OnPolicyRunner:
             self.obs_normalizer.load_state_dict(loaded["obs_norm_state_dict"])
         ac, sd = self.algorithm.actor_critic, loaded["model_state_dict"]
         ac.actor.load_state_dict({k[len("actor."):]: v for k, v in sd.items() if k.startswith("actor.")})
-        with torch.no_grad():
-            ac.std.copy_(sd["std"])
+        ac.assign_noise_std(sd["std"])
         self.algorithm.invalidate_graphs()
         self.current_learning_iteration = loaded["iter"]
         print(f"{path} is a distilled checkpoint: loaded the student's actor, std and actor-side normaliser / history; the critic is left as it "
               "is and the optimizer state is skipped")
         return loaded["infos"]
+
+    def _mean_actor(self):
+        """the module whose output is the mean action: the actor, or the first A of its 2A outputs under state_dependent_std"""
+        ac = self.algorithm.actor_critic
+        return ac.inference_actor() if self.state_dependent_std else ac.actor
 
     def get_inference_policy(self, device=None):
         self.algorithm.actor_critic.eval()
@@ -640,7 +684,7 @@ class OnPolicyRunner:
                     norm.to(device)
             return RecurrentPolicy(self.algorithm.actor_critic, norm)
         if self.privileged_actor:   # raw single PRIVILEGED frames in: the critic's history length and statistics
-            inner = self.algorithm.actor_critic.actor
+            inner = self._mean_actor()
             if self.empirical_normalization:
                 self.critic_obs_normalizer.eval()
                 inner = NormalizedPolicy(inner, self.critic_obs_normalizer)
@@ -652,7 +696,7 @@ class OnPolicyRunner:
                 norm.to(device)
             policy = lambda x: act(norm(x))
         if self.obs_history_length > 1:   # raw SINGLE frames in: the policy keeps its own history (policy.reset(dones) after every env.step)
-            inner = self.algorithm.actor_critic.actor
+            inner = self._mean_actor()
             if self.empirical_normalization:   # (history first, then the statistics as they are now)
                 inner = NormalizedPolicy(inner, self.obs_normalizer)
             policy = HistoryPolicy(inner, self.env.num_obs, self.obs_history_length).to(device if device is not None else self.device)

@@ -92,6 +92,12 @@ def get_args(argv=None):
                    help="The frame --rnd's networks read: the env's privileged frame (no observation noise) or the actor's raw frame")
     p.add_argument("--rnd_num_outputs", type=int, default=32, help="Width of --rnd's embedding (1..256)")
     p.add_argument("--rnd_learning_rate", type=float, default=1e-3, help="Learning rate of --rnd's predictor (fixed)")
+    p.add_argument("--noise_std_type", type=str, choices=["scalar", "log"],
+                   help="The action noise's parameter: std itself (scalar, default) or log_std with sigma = exp(log_std), which cannot reach "
+                        "zero (saved in the checkpoint; play needs the same value)")
+    p.add_argument("--state_dependent_std", action="store_true", default=False,
+                   help="The actor emits its own sigma per state: its output layer is [mean | s], sigma = s (scalar) or exp(s) (log; "
+                        "recommended).  Saved in the checkpoint; play needs the same flag")
     args = p.parse_args(argv)
     if args.obs_history < 1 or args.critic_obs_history < 1:
         raise ValueError(f"--obs_history and --critic_obs_history must be >= 1, got {args.obs_history} and {args.critic_obs_history}")
@@ -157,6 +163,10 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
         if getattr(args, "recurrent", False):   # (likewise: the policy config has no rnn_hidden_size otherwise)
             cfg_train.runner.policy_class_name = "ActorCriticRecurrent"
             cfg_train.policy.rnn_hidden_size = int(getattr(args, "rnn_hidden_size", 256))
+        if getattr(args, "noise_std_type", None) is not None:   # (likewise: the policy config has no such keys otherwise)
+            cfg_train.policy.noise_std_type = args.noise_std_type
+        if getattr(args, "state_dependent_std", False):   # (likewise)
+            cfg_train.policy.state_dependent_std = True
     return env_cfg, cfg_train
 
 
@@ -195,14 +205,17 @@ def export_policy_as_jit(actor_critic, path, normalizer=None, history=1):
     of the actor's layers (rl.recurrent.ExportedRecurrentPolicy: one raw frame per call, `reset_memory()` and `reset(dones)` exported).
     `normalizer` (an rl.normalizer.EmpiricalNormalization): the exported module takes RAW observations and normalises them itself.
     `history` > 1 (the runner's obs_history_length): it takes raw SINGLE frames and keeps the last `history` of them itself
-    (rl.history.HistoryPolicy: `reset_memory()` and `reset(dones)` are exported methods)"""
+    (rl.history.HistoryPolicy: `reset_memory()` and `reset(dones)` are exported methods).
+    An actor_critic with `state_dependent_std`: the exported module returns the mean, the first A of the actor's 2A outputs"""
     os.makedirs(path, exist_ok=True)
     path = os.path.join(path, "policy_jit.pt")
     if getattr(actor_critic, "is_recurrent", False):
         from ..rl.recurrent import ExportedRecurrentPolicy
         torch.jit.script(ExportedRecurrentPolicy(actor_critic, normalizer)).save(path)
         return path
-    model = copy.deepcopy(actor_critic.actor).to("cpu")
+    # (state_dependent_std: the actor's output layer is [mean | s]; the exported module slices, a consumer sees [B, A] as ever)
+    inner = actor_critic.inference_actor() if hasattr(actor_critic, "inference_actor") else actor_critic.actor
+    model = copy.deepcopy(inner).to("cpu")
     if normalizer is not None:
         from ..rl.normalizer import NormalizedPolicy
         model = NormalizedPolicy(model, copy.deepcopy(normalizer).to("cpu"))
