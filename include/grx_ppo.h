@@ -266,4 +266,7 @@ int grx_rnd_reward(int N, int E, const float* pred, const float* targ, float gam
 /* ... and a state-dependent action noise: the loss and the policy head for an actor whose output layer is [mean | s],
  * csrc/grx_ppo_noise.hip in the same library */
 #include "grx_ppo_noise.h"
+/* ... and the action-smoothness regulariser: the minibatch with its successor and perturbed rows, and the two smoothness
+ * losses, csrc/grx_ppo_smooth.hip in the same library */
+#include "grx_ppo_smooth.h"
 #endif

@@ -92,6 +92,14 @@ def load_ppo_library():
         lib.grx_ppo_loss_sd.argtypes = [C.c_int, C.c_int, fp, C.c_int] + [fp] * 8 + [C.c_float, C.c_float, C.c_float, C.c_int] + [fp] * 4 + [C.c_void_p]
         lib.grx_mlp_policy_head_sd.restype = C.c_int
         lib.grx_mlp_policy_head_sd.argtypes = [C.c_int] * 3 + [fp] * 3 + [C.c_int] + [fp] * 5 + [C.c_void_p]
+        # the action-smoothness regulariser (rl/smooth.py)
+        lib.grx_smooth_gather_rows.restype = C.c_int
+        lib.grx_smooth_gather_rows.argtypes = ([C.c_int, pp, pp, C.POINTER(C.c_int), fp, C.c_int, C.c_int, C.c_int, fp, C.c_int, C.c_int, fp,
+                                                C.c_float, fp, C.c_void_p])
+        lib.grx_smooth_loss_partials_size.restype = C.c_int
+        lib.grx_smooth_loss_partials_size.argtypes = [C.c_int, C.c_int]
+        lib.grx_smooth_loss.restype = C.c_int
+        lib.grx_smooth_loss.argtypes = [C.c_int, C.c_int, fp, C.c_int, C.c_int, fp, C.c_float, C.c_float, fp, fp, fp, C.c_void_p]
         _LIB = lib
     return _LIB
 

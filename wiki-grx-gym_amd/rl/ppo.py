@@ -68,7 +68,7 @@ class PPO:
                  value_loss_coef=1.0, entropy_coef=0.0, learning_rate=1e-3, learning_rate_min=1e-5, learning_rate_max=1e-2,
                  weight_decay=0.0, max_grad_norm=1.0, use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01,
                  device="cpu", storage_class="RolloutStorage", precision="fp32", symmetry=None, symmetry_coef=1.0, symmetry_maps=None,
-                 **kwargs):
+                 smooth=None, smooth_temporal_coef=0.1, smooth_spatial_coef=0.1, smooth_sigma=0.05, **kwargs):
         if kwargs:
             print("PPO.__init__ got unexpected arguments, which will be ignored: " + str(list(kwargs)))
         # precision="bf16": every hidden layer of actor and critic multiplies bf16 operands into fp32 accumulators -- in the rollout's
@@ -155,6 +155,13 @@ class PPO:
         self.symmetry, self._sym, self.symmetry_coef, self.mean_symmetry_loss = None, None, 0, 0.0
         if symmetry is not None:
             self._init_symmetry(symmetry, symmetry_coef, symmetry_maps)
+        # action smoothness (rl/smooth.py): "temporal" adds smooth_temporal_coef * mse(actor(s_t), actor(s_t+1)) over the pairs
+        # that are trajectory steps, "spatial" smooth_spatial_coef * mse(actor(s_t), actor(s_t + smooth_sigma * eps)), "both" both: the
+        # successor and the perturbed rows ride behind the minibatch's actor input.  Not a config key: `--smooth` / `--smooth_*` or an
+        # assignment to train_cfg.algorithm sets it; None runs nothing of it
+        self.smooth, self.mean_smooth_temporal, self.mean_smooth_spatial = None, 0.0, 0.0
+        if smooth is not None:
+            self._init_smooth(smooth, smooth_temporal_coef, smooth_spatial_coef, smooth_sigma)
         # random network distillation (rl/rnd.py): the runner builds it under `--rnd` and assigns it; None runs nothing of it
         self.rnd = None
         self.num_updates = 0
@@ -198,8 +205,29 @@ class PPO:
         self._sym_modes = [2, 2, 2, 1, 1, 1, 1, 2, 2] if symmetry in ("augment", "both") else [2, 0, 0, 0, 0, 0, 0, 0, 0]
         self._sym_tensor_maps = [maps.obs, maps.cobs, maps.actions, None, None, None, None, maps.actions, maps.sigma]
 
+    def _init_smooth(self, smooth, coef_t, coef_s, sigma):
+        from .smooth import blocks, check_values
+        succ, pert = blocks(smooth)
+        if self._recurrent:
+            raise ValueError("PPO: --smooth and --recurrent exclude each other: successor rows of a recurrent policy's minibatch are not implemented")
+        if self.symmetry is not None:
+            raise ValueError("PPO: --smooth and --symmetry exclude each other: both extend the minibatch")
+        if self._state_dependent:
+            raise ValueError("PPO: --smooth and --state_dependent_std exclude each other: a smoothness loss on the [mean | s] output is "
+                             "not implemented")
+        if _world() > 1:
+            raise NotImplementedError("PPO: --smooth with a world size above 1 is not implemented: it trains in one process only")
+        check_values(coef_t, coef_s, sigma)
+        self.smooth, self._smooth_succ, self._smooth_pert = smooth, succ, pert
+        self.smooth_temporal_coef, self.smooth_spatial_coef, self.smooth_sigma = float(coef_t), float(coef_s), float(sigma)
+        self._smooth_sum = torch.zeros(2, device=self.device)   # the update's sums of L_T and L_S (finite steps), read back once per update
+        self._smooth_bufs, self._smooth_bufs_gather, self._smooth_eps, self._smooth_valid = None, None, None, None
+
     def init_storage(self, num_envs, num_transitions_per_env, **_):
         ac = self.actor_critic
+        if self.smooth is not None and self._smooth_succ and num_transitions_per_env < 2:
+            raise ValueError(f"PPO: --smooth {self.smooth} with num_transitions_per_env={num_transitions_per_env}: a rollout of one step holds no "
+                             "successor row (use --smooth spatial or a longer rollout)")
         self.transition = RolloutStorage.Transition()
         if self._recurrent:
             from .recurrent import RecurrentRolloutStorage
@@ -417,6 +445,8 @@ class PPO:
             return self._update_recurrent()
         if self.symmetry is not None:
             return self._update_symmetry()
+        if self.smooth is not None:
+            return self._update_smooth()
         if self._device_lr:
             # For these GEMM shapes (batch ~10^4 rows, 39..512 columns, fp32) rocBLAS's kernel choices beat hipBLASLt's by 2x
             # on the weight-gradient products dY^T X (27-48 us against 66-73 us, tools/gpu_gemm_probe.py).  torch's BLAS
@@ -711,6 +741,102 @@ class PPO:
             self.learning_rate = float(self._lr_t.item())
         return host[0] / self.num_updates, host[1] / self.num_updates
 
+    # ------------------------------------------------------------------ action smoothness (rl/smooth.py)
+    def _smooth_rows(self):
+        return 1 + int(self._smooth_succ) + int(self._smooth_pert)
+
+    def _smooth_alloc(self, mb, width):
+        """the two buffers beside the minibatch: the step's noise eps [mb, W] (spatial) and the pairs' valid bytes [mb] (temporal)"""
+        self._smooth_eps = torch.zeros(mb, width, device=self.device) if self._smooth_pert else None
+        self._smooth_valid = torch.zeros(mb, dtype=torch.uint8, device=self.device) if self._smooth_succ else None
+
+    def _smooth_gatherer(self, srcs, dsts, draw=True):
+        """idx -> the minibatch in dsts, the successor / perturbed rows behind its actor input: one launch of grx_smooth_gather_rows on a HIP
+        device (GRX_SMOOTH_FUSED=0, CPU tensors: rl.smooth.smooth_gather_torch, the same arithmetic in torch).  draw: a fresh eps ~ N(0, 1)
+        from the device's generator in front of every gather (outside the captured step, next to the gather)"""
+        from .smooth import NoisyGather, SmoothGather, fused_enabled, smooth_gather_torch
+        st = self.storage
+        N, T, dones = st.num_envs, st.num_transitions_per_env, st.dones.reshape(-1)
+        args = (N, T, dones, self._smooth_succ, self._smooth_pert, self._smooth_eps, self.smooth_sigma, self._smooth_valid)
+        if srcs[0].is_cuda and fused_enabled():
+            gather = SmoothGather(srcs, dsts, *args)
+        else:
+            gather = lambda idx: smooth_gather_torch(srcs, dsts, idx, *args)
+        return NoisyGather(self._smooth_eps if draw else None, gather)
+
+    def _losses_smooth(self, obs, cobs, actions, target_values, advantages, returns, old_logp, old_mu, old_sigma):
+        """_losses on a minibatch whose actor input has the successor and / or the perturbed rows behind its mb rows: the PPO loss, the
+        critic and the KL see the mb rows there are, the actor runs on all of them, and coef_t L_T + coef_s L_S (grx_smooth_loss) joins the
+        loss."""
+        from .smooth import fused_enabled, smooth_loss
+        n = actions.shape[0]
+        mu, value = self._forward(obs, cobs)
+        surrogate_loss, value_loss, loss, kl_mean = self._loss_terms(mu[:n], value, actions, target_values, advantages, returns,
+                                                                     old_logp, old_mu, old_sigma)
+        sm, terms = smooth_loss(mu, self._smooth_succ, self._smooth_pert, self._smooth_valid, self.smooth_temporal_coef,
+                                self.smooth_spatial_coef, fused=fused_enabled())
+        loss = loss + sm
+        with torch.no_grad():   # (a step the NaN-skip drops adds nothing, as with the other statistics)
+            self._smooth_sum += torch.where(torch.isfinite(loss.detach()).reshape(1), terms, torch.zeros_like(terms))
+        return surrogate_loss, value_loss, loss, kl_mean
+
+    def _smooth_sources(self):
+        return self._sym_sources()   # (the same nine storage tensors, flattened to [T N, .])
+
+    def _update_smooth(self):
+        """update() with smoothness on: every minibatch is gathered WITH its extra actor rows into fixed buffers, and the step is the
+        captured one, the eager device one or the CPU one below"""
+        self._smooth_sum.zero_()
+        if self._device_lr:
+            with self._blas_for_update():
+                out = self._update_graphed() if self._use_graph else self._update_smooth_eager()
+        else:
+            out = self._update_smooth_eager()
+        host = self._smooth_sum.tolist()   # one extra 8-byte read-back per update
+        self.mean_smooth_temporal, self.mean_smooth_spatial = host[0] / self.num_updates, host[1] / self.num_updates
+        return out
+
+    def _update_smooth_eager(self):
+        """the eager paths, as _update_sym_eager: on a HIP device _update_graphed's loop with the step run, not replayed; on the CPU
+        update()'s host-side adaptive learning rate, NaN-skip, clip and Adam"""
+        st = self.storage
+        mb = st.num_envs * st.num_transitions_per_env // self.num_mini_batches
+        srcs = self._smooth_sources()
+        R = self._smooth_rows()
+        if self._smooth_bufs is None or self._smooth_bufs[0].shape[0] != R * mb or self._smooth_bufs[0].device != srcs[0].device:
+            self._smooth_bufs = [torch.zeros(mb * (R if t == 0 else 1), s.shape[1], device=s.device) for t, s in enumerate(srcs)]
+            self._smooth_alloc(mb, srcs[0].shape[1])
+            self._smooth_bufs_gather = None
+        key = tuple(s.data_ptr() for s in srcs)
+        if self._smooth_bufs_gather is None or self._smooth_bufs_gather[0] != key:
+            self._smooth_bufs_gather = (key, self._smooth_gatherer(srcs, self._smooth_bufs))
+        gather, bufs = self._smooth_bufs_gather[1], self._smooth_bufs
+        indices = torch.randperm(self.num_mini_batches * mb, requires_grad=False, device=self.device)   # RS:63-112: one permutation, reused
+        adaptive = self.desired_kl is not None and self.schedule == "adaptive"
+        sums = torch.zeros(3, device=self.device)        # value loss, surrogate loss, last KL
+        self.num_updates = self.num_learning_epochs * self.num_mini_batches
+        for _ in range(self.num_learning_epochs):
+            for i in range(self.num_mini_batches):
+                gather(indices[i * mb:(i + 1) * mb])
+                if self._device_lr:
+                    self._minibatch_step(bufs, sums)
+                    continue
+                surrogate_loss, value_loss, loss, kl_mean = self._losses_smooth(*bufs)
+                if adaptive:
+                    self._apply_kl(kl_mean.item())
+                if not torch.isfinite(loss):
+                    continue
+                self.optimizer.zero_grad()
+                loss.backward()
+                nn.utils.clip_grad_norm_(self.actor_critic.parameters(), self.max_grad_norm)
+                self.optimizer.step()
+                sums[0] += value_loss.detach(); sums[1] += surrogate_loss.detach()
+        host = sums.tolist()
+        if self._device_lr:
+            self.mean_kl = host[2]
+            self.learning_rate = float(self._lr_t.item())
+        return host[0] / self.num_updates, host[1] / self.num_updates
+
     def _update_device(self):
         """Same arithmetic as update(), no host round-trips inside the minibatch loop."""
         ac, multi = self.actor_critic, _collective_path()
@@ -759,6 +885,8 @@ class PPO:
         obs, cobs, actions, target_values, advantages, returns, old_logp, old_mu, old_sigma = batch
         adaptive = self.desired_kl is not None and self.schedule == "adaptive"
         losses = self._losses if self.symmetry is None else self._losses_sym
+        if self.smooth is not None:   # (the actor's input has R mb rows; the pairs' valid bytes are a static buffer beside the batch)
+            losses = self._losses_smooth
         surrogate_loss, value_loss, loss, kl_mean = losses(obs, cobs, actions, target_values, advantages, returns,
                                                            old_logp, old_mu, old_sigma)
         # grads dropped, not zero-filled: backward then WRITES each .grad (from the graph's private pool on replay) instead of
@@ -840,6 +968,9 @@ class PPO:
         widths = [st.observations.shape[-1], (st.pri_observations if st.pri_observations is not None else st.observations).shape[-1],
                   st.actions.shape[-1], 1, 1, 1, 1, st.mu.shape[-1], st.sigma.shape[-1]]
         rows = [mb] * len(widths) if self.symmetry is None else [mb * (2 if m else 1) for m in self._sym_modes]   # (symmetry: the mirrored half behind)
+        if self.smooth is not None:   # (smoothness: the successor / perturbed rows behind the actor's input, eps and valid beside the batch)
+            rows[0] = mb * self._smooth_rows()
+            self._smooth_alloc(mb, widths[0])
         self._static = [torch.zeros(r, w, device=dev) for r, w in zip(rows, widths)]
         self._sums = torch.zeros(3, device=dev)
         # warm-up runs real optimizer steps (allocator / lazy-state initialisation): snapshot and restore everything they touch
@@ -928,16 +1059,23 @@ class PPO:
         self._sums.zero_()
         if self.symmetry is not None:
             self._sym_sum.zero_()   # (the dry runs of a capture added to it)
+        if self.smooth is not None:
+            self._smooth_sum.zero_()   # (likewise)
         multi = _collective_path()
         gather = None
         if self._fused_store:   # (libgrx_ppo.so is in use)
             key = tuple(s.data_ptr() for s in srcs) + tuple(b.data_ptr() for b in self._static)
             if getattr(self, "_gather_key", None) != key:
                 from .fused_loss import RowGather
-                self._gather, self._gather_key = (RowGather(srcs, self._static) if self.symmetry is None else self._sym_gatherer(srcs, self._static)), key
+                if self.smooth is not None:
+                    self._gather, self._gather_key = self._smooth_gatherer(srcs, self._static), key
+                else:
+                    self._gather, self._gather_key = (RowGather(srcs, self._static) if self.symmetry is None else self._sym_gatherer(srcs, self._static)), key
             gather = self._gather
         elif self.symmetry is not None:
             gather = self._sym_gatherer(srcs, self._static)
+        elif self.smooth is not None:
+            gather = self._smooth_gatherer(srcs, self._static)
         for _ in range(self.num_learning_epochs):
             for i in range(self.num_mini_batches):
                 idx = indices[i * mb:(i + 1) * mb]

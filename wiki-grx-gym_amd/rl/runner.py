@@ -104,6 +104,11 @@ class OnPolicyRunner:
             self.noise = {"std_type": self.noise_std_type, "state_dependent": self.state_dependent_std}
         if self.recurrent:
             self._check_recurrent()
+        # action smoothness: the CAPS regulariser on the actor's mean in PPO's update.  Not config keys either (`--smooth` /
+        # `--smooth_*` or assignments to train_cfg.algorithm set them); nothing of it is saved
+        self.smooth = self.algorithm_cfg.get("smooth") or None
+        if self.smooth is not None:
+            self._check_smooth()
         if self.distill_from is not None:
             teacher = self._check_distillation(env, device)
         self.obs_history = self.critic_obs_history = None
@@ -370,6 +375,28 @@ class OnPolicyRunner:
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise NotImplementedError("--symmetry with a world size above 1 is not implemented: it trains in one process only")
 
+    def _check_smooth(self):
+        """what --smooth does not combine with"""
+        from .smooth import blocks, check_values
+        succ, _ = blocks(self.smooth)
+        if self.recurrent:
+            raise ValueError("--smooth and --recurrent exclude each other: successor rows of a recurrent policy's minibatch are not implemented")
+        if self.symmetry is not None:
+            raise ValueError("--smooth and --symmetry exclude each other: both extend the minibatch")
+        if self.state_dependent_std:
+            raise ValueError("--smooth and --state_dependent_std exclude each other: a smoothness loss on the [mean | s] output is not implemented")
+        if self.distill_from is not None:
+            raise ValueError("--smooth and --distill_from exclude each other: a distillation run has no PPO loss to add to")
+        if bool(self.cfg.get("exact_resume", False)):
+            raise NotImplementedError("--smooth with --exact_resume: the perturbation's draws are not part of the resumed step order")
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("--smooth with a world size above 1 is not implemented: it trains in one process only")
+        a = self.algorithm_cfg
+        check_values(a.get("smooth_temporal_coef", 0.1), a.get("smooth_spatial_coef", 0.1), a.get("smooth_sigma", 0.05), who="runner")
+        if succ and int(self.cfg["num_steps_per_env"]) < 2:
+            raise ValueError(f"--smooth {self.smooth} with num_steps_per_env={self.cfg['num_steps_per_env']}: a rollout of one step holds no "
+                             "successor row (use --smooth spatial or a longer rollout)")
+
     def _check_rnd(self, env, rnd_cfg):
         """what --rnd does not combine with"""
         from .rnd import STATES
@@ -465,6 +492,9 @@ class OnPolicyRunner:
             w.add_scalar("Loss/kl", alg.mean_kl, it)
             if self.symmetry is not None:
                 w.add_scalar("Loss/symmetry", alg.mean_symmetry_loss, it)
+            if self.smooth is not None:
+                w.add_scalar("Loss/smooth_temporal", alg.mean_smooth_temporal, it)
+                w.add_scalar("Loss/smooth_spatial", alg.mean_smooth_spatial, it)
             if self.rnd is not None:
                 w.add_scalar("Loss/rnd", locs["mean_rnd_loss"], it)
                 w.add_scalar("Train/mean_intrinsic_reward", locs["mean_intrinsic_reward"], it)

@@ -78,6 +78,13 @@ def get_args(argv=None):
     p.add_argument("--symmetry", type=str, choices=["augment", "loss", "both"],
                    help="Left-right symmetry in PPO's update: mirrored minibatches (augment), a mirror loss (loss) or both; nothing is saved")
     p.add_argument("--symmetry_coef", type=float, default=1.0, help="Weight of --symmetry's mirror loss (loss / both; default 1.0)")
+    p.add_argument("--smooth", type=str, choices=["temporal", "spatial", "both"],
+                   help="Action-smoothness regularisation (CAPS) in PPO's update: the mean action at s_t close to the one at s_t+1 (temporal), "
+                        "to the one at s_t + sigma * noise (spatial), or both; nothing is saved")
+    p.add_argument("--smooth_temporal_coef", type=float, default=0.1, help="Weight of --smooth's temporal term (default 0.1, not tuned)")
+    p.add_argument("--smooth_spatial_coef", type=float, default=0.1, help="Weight of --smooth's spatial term (default 0.1, not tuned)")
+    p.add_argument("--smooth_sigma", type=float, default=0.05,
+                   help="Standard deviation of --smooth's perturbation of the actor's (stacked, normalised) input (default 0.05, not tuned)")
     p.add_argument("--rnd", action="store_true", default=False,
                    help="Random network distillation: an intrinsic reward (predictor error against a fixed random network) added to the env's")
     p.add_argument("--rnd_weight", type=float, default=0.1, help="Weight of --rnd's intrinsic reward (default 0.1, not tuned)")
@@ -151,6 +158,12 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
         if getattr(args, "symmetry", None) is not None:   # (likewise: the algorithm config has no such keys otherwise)
             cfg_train.algorithm.symmetry = args.symmetry
             cfg_train.algorithm.symmetry_coef = float(getattr(args, "symmetry_coef", 1.0))
+        if getattr(args, "smooth", None) is not None:   # (likewise; the --smooth_* values travel only with --smooth)
+            a = cfg_train.algorithm
+            a.smooth = args.smooth
+            a.smooth_temporal_coef = float(getattr(args, "smooth_temporal_coef", 0.1))
+            a.smooth_spatial_coef = float(getattr(args, "smooth_spatial_coef", 0.1))
+            a.smooth_sigma = float(getattr(args, "smooth_sigma", 0.05))
         if getattr(args, "rnd", False):   # (likewise; the --rnd_* values travel only with --rnd)
             a = cfg_train.algorithm
             a.rnd = True
