@@ -21,6 +21,10 @@ int grx_ppo_loss_partials_size(int batch);
  *   out[4]      = { surrogate loss, value loss, total loss, mean KL(old || new) }
  *   d_mu [batch][num_actions], d_std [num_actions], d_value [batch] = d(total loss)/d(.)
  *   total loss = surrogate + value_loss_coef * value_loss - entropy_coef * mean entropy   (ppo.py:243)
+ * Where inputs leave the finite range (a sigma that underflows, is 0, negative, inf or NaN; a ratio that overflows; infinite
+ * advantages, returns or values) the loss and the mean KL are finite exactly where the fp32 torch spelling's are, and a gradient entry
+ * is non-finite exactly where torch.autograd's is -- including the NaN that `sigma = mean * 0.0 + std` hands every d_mu entry whose
+ * d sigma is not finite.  A finite loss never hides a non-finite gradient; grx_ppo_step_tail skips the step on either.
  * `stream` is a hipStream_t (0 = the null stream).  Returns 0, or a negative number for invalid arguments
  * (num_actions outside 1..32, batch < 1) -- nothing is launched then.
  */
@@ -80,6 +84,13 @@ int grx_ppo_store_transition(int N, int num_obs, int num_pri, int num_actions,
  *             formulas); unless the loss is not finite: Adam on its chunk with the CLIPPED gradient -- the arithmetic of ATen's
  *             fused_adam_utils.cuh adam_math (double constants, float state), bias corrections from the step counter; block 0: the
  *             update's running statistics sums[0] += value_loss, sums[1] += surrogate_loss (finite steps only), sums[2] = kl.
+ * A step is SKIPPED when the loss is not finite, when *bad_flag != 0, or when the gradients' total norm as launch 2 computes it in fp32 is
+ * not finite: a NaN or +-inf gradient element, or finite elements whose fp32 sum of squares overflows.  A skipped step leaves parameters,
+ * both moments and the step counters bit-identical (launch 1 has counted the step before the norm is known; launch 2's block of each
+ * tensor's first elements takes that back, exact below 2^24 steps), adds nothing to sums[0] / sums[1], and still writes sums[2] = kl and
+ * the learning rate.  This is the rule of PPO's multi-rank paths (a non-finite gradient bucket skips).  It departs from torch on purpose:
+ * clip_grad_norm_ + fused Adam with found_inf = !isfinite(loss) poisons every parameter on a NaN norm and, on an infinite one (clip
+ * coefficient 0), takes an Adam step on zero gradients; PPO's torch tails fold !isfinite(total norm) into found_inf to agree with this.
  * weight_decay = 0, no amsgrad, no maximize (the reference's optimizer).  Tensor pointers travel BY VALUE in the launch arguments: a captured
  * graph keeps the addresses of its capture (PyTorch's graph pool keeps gradient buffers where they were).  All pointers: device memory. */
 #define GRX_PPO_TAIL_MAX 24
@@ -90,7 +101,7 @@ typedef struct grx_ppo_tail_tensors {
     long long numel[GRX_PPO_TAIL_MAX];
 } grx_ppo_tail_tensors;
 typedef struct grx_ppo_tail_args {
-    const float* loss;                      /* total loss of the minibatch: a non-finite one skips the step */
+    const float* loss;                      /* total loss of the minibatch: a non-finite one skips the step (so does a non-finite gradient norm) */
     const float* bad_flag;                  /* optional: != 0 skips the step too (the multi-rank path's collective decision) */
     const float* kl;                        /* minibatch mean KL */
     float* lr;                              /* learning rate, in / out */

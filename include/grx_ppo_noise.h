@@ -12,7 +12,8 @@ extern "C" {
  * grx_ppo_loss_sd: grx_ppo_loss for such a policy.  raw, d_raw: [batch][2A]; every other argument as in grx_ppo_loss, `out` included.
  * grx_ppo_loss's arithmetic term by term with m = raw[i][k], s = raw[i][A + k] (the same NaN propagation through max / clamp, the same
  * tie and clamp gradient rules, batch sums in double, block partials added in block order by a finalize launch).  The entropy is a fourth
- * batch sum: the mean over rows of sum_k (1/2 + 1/2 log 2 pi + log sigma_ik), where log sigma is s itself under `log`.  The gradient of
+ * batch sum: the mean over rows of sum_k (1/2 + 1/2 log 2 pi + log sigma_ik), where log sigma is s itself under `log` (where expf(s)
+ * saturates to inf or 0 it is logf of that, +-inf as torch's: a finite loss must not stand over such a row).  The gradient of
  * the total loss lands on the raw output:
  *     d_raw[i][k]     = g_logp df / sigma^2                                    (grx_ppo_loss's d_mu expression)
  *     d sigma         = g_logp (df^2 / sigma^3 - 1 / sigma) - entropy_coef / (batch sigma)

@@ -58,6 +58,64 @@ def ppo_loss_ref(mu, std, value, actions, old_logp, old_mu, old_sigma, advantage
     return {"out": out, "d_mu": d_mu, "d_std": d_std, "d_value": d_value.reshape(value.shape), "scale": scale}
 
 
+class TorchSpelling:
+    """PPO's own fp32 torch spelling of the minibatch loss on the inputs' device -- the branch PPO._losses takes with the fused loss off,
+    differentiated by autograd -- as the reference where float64 cannot serve: at the extremes, underflow of sigma^2 and overflow of exp are
+    fp32 facts.  The networks of a real PPO are replaced by identities, so that _losses' `obs` IS the actor's output (mu [B, A], or the raw
+    [mean | s] of a state-dependent sigma: noise "scalar" / "log" with state_dependent) and `cobs` the critic's."""
+
+    def __init__(self, A, clip, value_loss_coef, entropy_coef, use_clipped_value_loss, device, noise="scalar", state_dependent=False):
+        from wiki_grx_gym_amd.rl.modules import ActorCriticMLP
+        from wiki_grx_gym_amd.rl.ppo import PPO
+        ac = ActorCriticMLP(1, 1, A, actor_hidden_dims=[1], critic_hidden_dims=[1], noise_std_type=noise, state_dependent_std=state_dependent)
+        self.alg = PPO(ac, clip_param=clip, value_loss_coef=value_loss_coef, entropy_coef=entropy_coef,
+                       use_clipped_value_loss=use_clipped_value_loss, schedule="adaptive", desired_kl=0.01, device=device)
+        self.alg._fused_loss = False
+        ac.actor = ac.critic = torch.nn.Identity()
+        self.ac, self.state_dependent = ac, state_dependent
+
+    def __call__(self, mu, std, value, actions, old_logp, old_mu, old_sigma, advantages, returns, target_values):
+        """dict: out = [surrogate, value_loss, total, mean KL] (fp32), d_mu (d_raw when state-dependent), d_std (None then), d_value"""
+        assert not self.alg._loss_is_fused()
+        mu, value = mu.detach().clone().requires_grad_(), value.detach().clone().requires_grad_()
+        if not self.state_dependent:
+            with torch.no_grad():
+                self.ac.std.copy_(std)
+            self.ac.std.grad = None
+        s, v, loss, kl = self.alg._losses(mu, value, actions, target_values, advantages, returns, old_logp, old_mu, old_sigma)
+        loss.backward()
+        d_std = None if self.state_dependent else self.ac.std.grad.detach().clone()
+        return {"out": torch.stack([s, v, loss, kl]).detach(), "d_mu": mu.grad, "d_std": d_std, "d_value": value.grad}
+
+
+def same_non_finite(a, b):
+    """two scalars: both finite, both NaN, or the same infinity"""
+    a, b = float(a), float(b)
+    if math.isfinite(a) or math.isfinite(b):
+        return math.isfinite(a) and math.isfinite(b)
+    return (math.isnan(a) and math.isnan(b)) or a == b
+
+
+def check_extremes(got, want, tag):
+    """A loss kernel's (out [4], d_mu, d_std or None, d_value) against TorchSpelling's dict where values stop being finite:
+    1. out[2] is finite exactly when torch's loss is, and a non-finite one is the same NaN / infinity; the same for out[3], the mean KL;
+    2. a finite torch loss over a torch gradient with a non-finite entry: the kernel's matching gradient has one too (the step tail's
+       skip on a non-finite gradient norm then drops the step);
+    3. the non-finite masks of d_mu and d_value are equal entry for entry, d_std's per action."""
+    out, d_mu, d_std, d_value = got
+    for i, name in ((2, "loss"), (3, "kl")):
+        assert same_non_finite(out[i], want["out"][i]), (tag, name, float(out[i]), float(want["out"][i]))
+    pairs = [("d_mu", d_mu, want["d_mu"]), ("d_value", d_value.reshape(-1), want["d_value"].reshape(-1))]
+    if d_std is not None:
+        pairs.append(("d_std", d_std, want["d_std"]))
+    if math.isfinite(float(want["out"][2])):
+        for name, g, w in pairs:
+            assert bool(torch.isfinite(w).all()) or not bool(torch.isfinite(g).all()), (tag, name, "the kernel hides a non-finite gradient")
+    for name, g, w in pairs:
+        mg, mw = ~torch.isfinite(g), ~torch.isfinite(w)
+        assert torch.equal(mg, mw), (tag, name, "non-finite entries: kernel", int(mg.sum()), "torch", int(mw.sum()), "differing", int((mg != mw).sum()))
+
+
 def loss_near_ties(mu, std, value, actions, old_logp, returns, target_values, clip, margin=1e-3):
     """Rows whose float64 arithmetic lies within `margin` of a branch of the loss, where fp32 rounding may take the other one:
     a ratio near 1 - clip or 1 + clip (clamp's gradient switches), |value - target| near clip, and -- with the value clipped --
@@ -108,10 +166,17 @@ def step_tail_ref(params, grads, exp_avg, exp_avg_sq, steps, lr, loss, bad_flag,
     NaN-skip, nn.utils.clip_grad_norm_ (norm of the per-tensor 2-norms, max_norm / (total + 1e-6) clamped to 1, every
     gradient scaled) and torch.optim.Adam.step() (no weight decay / amsgrad / maximize; bias corrections from the step
     counter after its increment).  `lr` is the learning rate in force for this step.  Lists of tensors in, new lists out
-    (params, exp_avg, exp_avg_sq, steps as float64) plus the total norm and the clip coefficient."""
+    (params, exp_avg, exp_avg_sq, steps as float64) plus the total norm and the clip coefficient.
+
+    The skip rule (include/grx_ppo.h): a non-finite loss, bad_flag != 0, or a gradient whose total norm is not finite in fp32 -- any
+    non-finite element, or a float64 sum of squares above the largest float32 (callers keep that sum a factor of 10 away from the
+    boundary, so the kernel's fp32 sum falls on the same side).  Where torch takes a zero-gradient Adam step (the overflow) this skips."""
     P, G, M, V = ([_d(t) for t in ts] for ts in (params, grads, exp_avg, exp_avg_sq))
     S = [float(s) for s in steps]
     bad = (not math.isfinite(float(loss))) or (bad_flag is not None and float(bad_flag) != 0.0)
+    bad = bad or not all(bool(torch.isfinite(g).all()) for g in G)
+    sumsq = sum(float((g * g).sum()) for g in G)
+    bad = bad or not sumsq <= float(np.finfo(np.float32).max)
     norms = torch.stack([g.reshape(-1).norm(2.0) for g in G])
     total = float(norms.norm(2.0))
     clip = min(max_grad_norm / (total + 1e-6), 1.0)

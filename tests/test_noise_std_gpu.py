@@ -78,11 +78,13 @@ def _fused_sd(d, log_std, use_clipped):
     return out.detach(), raw.grad, value.grad
 
 
-def _tolerances(d, ref, log_std):
+def _tolerances(d, ref, log_std, rows=None):
     """_check_loss's tolerances (tests/test_ppo_kernels_gpu.py) with a sigma per row.  A row's ratio = exp(logp - old_logp), logp an fp32
     sum of A terms: relative error <= R_row = U32 ((A + 4) sum_k |term_k| + 2 |old_logp| + 8) with the row's own sigma; everything per
     row inherits it.  The batch sums run in double: the per-row error summed, <= R * (sum of the rows' magnitudes), plus the final
-    rounding; the value loss is a difference of its operands squared, the KL row and the entropy row fp32 sums of A terms."""
+    rounding; the value loss is a difference of its operands squared, the KL row and the entropy row fp32 sums of A terms.
+    rows (a bool mask [B]): the gradient halves' largest magnitude is taken over those rows only (the others hold planted values that
+    are not finite; only "mean", "s" and "d_value" on those rows mean anything then)."""
     B, A = d["actions"].shape
     mu, sigma, a = d["raw"][:, :A].double(), ref["sigma"], d["actions"].double()
     terms = -(a - mu) ** 2 / (2.0 * sigma ** 2) - torch.log(sigma) - R.LOG_SQRT_2PI
@@ -90,7 +92,7 @@ def _tolerances(d, ref, log_std):
     Rmax = float(R_row.max())
     halves = []
     for half in (ref["d_raw"][:, :A], ref["d_raw"][:, A:]):
-        halves.append(R_row.unsqueeze(-1) * half.abs() + 4 * U32 * float(half.abs().max()))
+        halves.append(R_row.unsqueeze(-1) * half.abs() + 4 * U32 * float((half if rows is None else half[rows]).abs().max()))
     ops = d["value"].double().abs() + d["target_values"].double().abs() + d["returns"].double().abs() + CLIP
     tol_value = 16 * U32 * 2.0 * VCOEF / B * ops
     os_, om = d["old_sigma"].double(), d["old_mu"].double()
@@ -198,6 +200,105 @@ def test_loss_sd_rejects_invalid_arguments_and_is_deterministic():
     assert call() == 0
     torch.cuda.synchronize()
     assert all(torch.equal(first[k], outs[k]) for k in outs)
+
+
+# ---- grx_ppo_loss_sd where values stop being finite ---------------------------------------------------------------------------------------
+XB, XROWS = 257, (0, 255, 256)   # two blocks, the second of one row; planted rows: the first, and the last of either block
+_NAN, _INF = float("nan"), float("inf")
+# name: what is planted in rows XROWS ("s": column k of raw's s half; [B, A] tensors: column k).  tests/test_ppo_kernels_gpu.py's EXTREMES
+# with the sigma of a row planted through its s, and the values of s the issue of a state-dependent sigma adds.
+SD_ROW_EXTREMES = {
+    "ratio_overflow_adv_pos": {"old_logp": -200.0, "advantages": 1.5},
+    "ratio_overflow_adv_neg": {"old_logp": -200.0, "advantages": -1.5},
+    "ratio_overflow_adv_zero": {"old_logp": -200.0, "advantages": 0.0},
+    "ratio_large_finite": {"old_logp": -70.0},
+    "adv_pinf": {"advantages": _INF},
+    "adv_ninf": {"advantages": -_INF},
+    "returns_inf": {"returns": _INF},
+    "value_inf": {"value": _INF},
+    "target_values_inf": {"target_values": _INF},
+    "kl_only": {"old_sigma": 0.0},
+}
+SD_S_EXTREMES = {
+    # `scalar`: sigma = s.  sigma^2 = 1e-50 = 0; sigma^2 = 1e-36 normal, sigma^3 = 0; invalid sigmas
+    False: {"s_1e-25": 1e-25, "s_1e-18": 1e-18, "s_zero": 0.0, "s_negative": -0.3, "s_inf": _INF, "s_nan": _NAN},
+    # `log`: sigma = exp(s).  exp(-57.5) = 1e-25 and exp(-41.4) = 1e-18 as above; exp(100) = inf; exp(-100) = 0 up to a subnormal
+    True: {"s_log_1e-25": -57.5, "s_log_1e-18": -41.4, "s_plus_100": 100.0, "s_minus_100": -100.0, "s_inf": _INF, "s_minus_inf": -_INF, "s_nan": _NAN},
+}
+
+
+def _sd_extreme_data(A, seed, log_std):
+    """tests/test_ppo_kernels_gpu.py's _extreme_data with raw = [mu | s], s = 0.3 or log(0.3) in every row"""
+    g = _gen(seed)
+    mk = lambda *s: torch.randn(*s, device=DEV, generator=g)
+    B = XB
+    mu, sigma = mk(B, A) * 0.1, torch.full((B, A), 0.3, device=DEV)
+    d = dict(value=mk(B, 1), actions=mk(B, A) * 0.3, old_logp=mk(B, 1) * 0.1 - 2, old_mu=mk(B, A) * 0.1, old_sigma=sigma.clone(),
+             advantages=mk(B, 1), returns=mk(B, 1), target_values=mk(B, 1))
+    ties = lambda: ppo_ref.loss_near_ties(mu, sigma, d["value"], d["actions"], d["old_logp"], d["returns"], d["target_values"], CLIP)
+    for _ in range(20):
+        bad = ties()
+        if not bool(bad.any()):
+            break
+        b = bad.reshape(-1, 1)
+        d["old_logp"] = torch.where(b, d["old_logp"] - 0.01, d["old_logp"])
+        d["target_values"] = torch.where(b, d["target_values"] + 0.013, d["target_values"])
+        d["returns"] = torch.where(b, d["returns"] + 0.011, d["returns"])
+    assert not bool(ties().any())
+    d["raw"] = torch.cat([mu, torch.log(sigma) if log_std else sigma], 1).contiguous()
+    return d
+
+
+def _sd_cases():
+    return [(log_std, name) for log_std in (False, True) for name in list(SD_ROW_EXTREMES) + list(SD_S_EXTREMES[log_std])]
+
+
+@pytest.mark.parametrize("log_std,case", _sd_cases(), ids=[f"{'log' if l else 'scalar'}-{c}" for l, c in _sd_cases()])
+def test_loss_sd_at_the_extremes_shows_what_torch_shows(log_std, case):
+    """grx_ppo_loss_sd as tests/test_ppo_kernels_gpu.py::test_loss_at_the_extremes_shows_what_torch_shows judges grx_ppo_loss: B = 257,
+    A in {1, 10, 32}, the value loss clipped and not, against PPO's own fp32 torch spelling of a state-dependent sigma on the device
+    (ppo_ref.TorchSpelling), the extremes planted in rows 0, 255 and 256.  ppo_ref.check_extremes: loss and mean KL finite exactly when
+    torch's are and non-finite in the same way, no non-finite torch gradient hidden under a finite loss, the non-finite masks of d_raw and
+    d_value equal entry for entry.  Every other row of d_raw and d_value meets _tolerances' float64 bound: a planted row does not leak.
+    The large finite ratio is an ordinary case for the float64 comparison of test_loss_sd_matches_float64.  No planted value had to be
+    moved.  (Found by this: log-s_plus_100 -- the kernel's loss 5.77 where torch's is -inf, log sigma taken as s = 100 under a sigma of
+    inf; scalar-s_inf -- torch's d s NaN (2 sigma * 0), the kernel's 0; target_values_inf -- d_value NaN where torch has 0.  Fixed in
+    the kernel.)"""
+    for A in (1, 10, 32):
+        k = A // 2
+        d = _sd_extreme_data(A, 7100 + A + (7 if log_std else 0), log_std)
+        rows_i = list(XROWS)
+        if case in SD_ROW_EXTREMES:
+            for name, v in SD_ROW_EXTREMES[case].items():
+                if d[name].shape[1] == 1:
+                    d[name][rows_i] = v
+                else:
+                    d[name][rows_i, k] = v
+        else:
+            d["raw"][rows_i, A + k] = SD_S_EXTREMES[log_std][case]
+        rows = torch.ones(XB, dtype=torch.bool, device=DEV)
+        rows[rows_i] = False
+        for use_clipped in (True, False):
+            tag = (case, A, log_std, use_clipped)
+            args = (d["value"], d["actions"], d["old_logp"], d["old_mu"], d["old_sigma"], d["advantages"], d["returns"], d["target_values"])
+            ref = R.loss_sd_ref(d["raw"], log_std, *args, CLIP, VCOEF, ECOEF, use_clipped)
+            out, d_raw, d_value = _fused_sd(d, log_std, use_clipped)
+            finite_case = case == "ratio_large_finite"
+            tol = _tolerances(d, ref, log_std, None if finite_case else rows)
+            keep = torch.ones_like(rows) if finite_case else rows
+            for name, got, want, t in (("d_raw mean half", d_raw[:, :A], ref["d_raw"][:, :A], tol["mean"]), ("d_raw s half", d_raw[:, A:], ref["d_raw"][:, A:], tol["s"]),
+                                       ("d_value", d_value, ref["d_value"], tol["d_value"])):
+                err = (got.double() - want).abs()[keep]
+                assert bool(torch.isfinite(t[keep]).all()) and bool((err <= t[keep]).all()), (tag, name, float((err / t[keep]).max()))
+            if finite_case:
+                err = (out.double() - ref["out"]).abs()
+                assert bool((err <= tol["out"]).all()), (tag, "out", out.tolist(), ref["out"].tolist(), (err / tol["out"]).tolist())
+                continue
+            want = ppo_ref.TorchSpelling(A, CLIP, VCOEF, ECOEF, use_clipped, DEV, noise="log" if log_std else "scalar", state_dependent=True)(
+                d["raw"], None, d["value"], d["actions"], d["old_logp"], d["old_mu"], d["old_sigma"], d["advantages"], d["returns"], d["target_values"])
+            print(tag, "kernel", out.tolist(), "torch", want["out"].tolist(), "non-finite d_raw / d_value: kernel",
+                  [int((~torch.isfinite(x)).sum()) for x in (d_raw, d_value)], "torch", [int((~torch.isfinite(want[n])).sum()) for n in ("d_mu", "d_value")])
+            ppo_ref.check_extremes((out, d_raw, None, d_value), want, tag)
 
 
 # ---- grx_mlp_policy_head_sd ---------------------------------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 """The fused PPO minibatch loss (libgrx_ppo.so, include/grx_ppo.h) against the torch expression it replaces
 (rsl_rl/algorithms/ppo.py:215-245 spelled with torch.distributions.Normal): values and gradients."""
+import math
 import os
 
 import pytest
@@ -375,9 +376,14 @@ def test_fused_loss_propagates_nan_like_torch():
     _toy_rollout(a, 0)
     a.storage.values[3, 5] = float("nan")
     before = [p.detach().clone() for p in a.actor_critic.parameters()]
-    a.update()
+    losses = a.update()
     after = list(a.actor_critic.parameters())
     assert all(torch.isfinite(p).all() for p in after)
+    # 4 minibatches x 2 epochs, the planted row in one minibatch of each epoch: exactly those two steps are skipped, the other six run
+    steps = [float(a.optimizer.state[p]["step"]) for p in after]
+    assert steps == [6.0] * len(after), steps
+    assert all(not torch.equal(p, b) for p, b in zip(after, before))
+    assert len(losses) == 2 and all(math.isfinite(v) for v in losses), losses
 
 
 @pytest.mark.parametrize("M,K,N", [(4096, 39, 512), (4096, 168, 512), (4096, 512, 256), (4096, 256, 128), (4100, 130, 96), (70, 33, 64),

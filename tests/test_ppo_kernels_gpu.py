@@ -102,7 +102,10 @@ def _fused(d, use_clipped):
     return out.detach(), mu.grad, std.grad, value.grad
 
 
-def _check_loss(d, use_clipped, tag):
+def _check_loss(d, use_clipped, tag, rows=None):
+    """grx_ppo_loss on `d` against ppo_ref.ppo_loss_ref.  rows (a bool mask [B]): only those rows of d_mu and d_value are judged, with the
+    same formulas and d_mu's largest magnitude taken over them -- the other rows hold planted values that are not finite, and so are the
+    batch sums."""
     out, d_mu, d_std, d_value = _fused(d, use_clipped)
     ref = ppo_ref.ppo_loss_ref(d["mu"], d["std"], d["value"], d["actions"], d["old_logp"], d["old_mu"], d["old_sigma"], d["advantages"],
                                d["returns"], d["target_values"], CLIP, VCOEF, ECOEF, use_clipped)
@@ -113,14 +116,17 @@ def _check_loss(d, use_clipped, tag):
     terms = -(a - mu) ** 2 / (2.0 * std ** 2) - torch.log(std) - ppo_ref.LOG_SQRT_2PI
     R_row = U32 * ((A + 4) * terms.abs().sum(-1) + 2.0 * d["old_logp"].double().abs().reshape(-1) + 8.0)
     R = float(R_row.max())
-    err = (d_mu.double() - ref["d_mu"]).abs()
-    tol = R_row.unsqueeze(-1) * ref["d_mu"].abs() + 4 * U32 * float(ref["d_mu"].abs().max())
-    assert bool((err <= tol).all()), (tag, "d_mu", float((err / tol).max()))
+    keep = torch.ones(B, dtype=torch.bool, device=DEV) if rows is None else rows
+    err = (d_mu.double() - ref["d_mu"]).abs()[keep]
+    tol = (R_row.unsqueeze(-1) * ref["d_mu"].abs())[keep] + 4 * U32 * float(ref["d_mu"][keep].abs().max())
+    assert bool(torch.isfinite(tol).all()) and bool((err <= tol).all()), (tag, "d_mu", float((err / tol).max()))
     # the value gradient: a few fp32 operations on v, tv, ret, clip -- relative to those operands' size
     ops = d["value"].double().abs() + d["target_values"].double().abs() + d["returns"].double().abs() + CLIP
-    err = (d_value.double() - ref["d_value"]).abs()
-    tol = 16 * U32 * 2.0 * VCOEF / B * ops
-    assert bool((err <= tol).all()), (tag, "d_value", float((err / tol).max()))
+    err = (d_value.double() - ref["d_value"]).abs()[keep]
+    tol = (16 * U32 * 2.0 * VCOEF / B * ops)[keep]
+    assert bool(torch.isfinite(tol).all()) and bool((err <= tol).all()), (tag, "d_value", float((err / tol).max()))
+    if rows is not None:
+        return
     # sums over the batch run in double: the error is the per-row error summed, <= R * (sum of the rows' magnitudes), plus the final rounding
     err = (d_std.double() - ref["d_std"]).abs()
     tol = R * ref["scale"]["d_std"] + 2 * U32 * ref["d_std"].abs()
@@ -174,6 +180,101 @@ def test_loss_rejects_invalid_arguments_and_writes_nothing():
     for t in (out, d_mu, d_std, d_value, partials):
         assert bool((t == sentinel).all())
     assert lib.grx_ppo_loss_partials_size(0) == 0
+
+
+# ---- grx_ppo_loss where values stop being finite ------------------------------------------------------------------------------------
+XB, XROWS = 257, (0, 255, 256)   # two blocks, the second of one row; planted rows: the first, and the last of either block
+_NAN, _INF = float("nan"), float("inf")
+# name: (what is planted, per-row?).  "std": std[k] = value for one action k (every row sees it); the rest: rows XROWS of the named tensors.
+# Every planted value sits far from an fp32 threshold: sigma^2 = 1e-50 is 0 (the smallest subnormal is 1.4e-45) and 1e-36 normal with
+# sigma^3 = 1e-54 = 0; exp(200 + logp) overflows for any logp these rows have (exp overflows at 88.7) and exp(70 + logp) does not (the
+# rows' logp stays below 14: asserted).
+EXTREMES = {
+    "sigma_sq_underflow": ({"std": 1e-25}, False),
+    "sigma_cube_underflow": ({"std": 1e-18}, False),
+    "sigma_zero": ({"std": 0.0}, False),
+    "sigma_negative": ({"std": -0.3}, False),
+    "sigma_inf": ({"std": _INF}, False),
+    "sigma_nan": ({"std": _NAN}, False),
+    "ratio_overflow_adv_pos": ({"old_logp": -200.0, "advantages": 1.5}, True),
+    "ratio_overflow_adv_neg": ({"old_logp": -200.0, "advantages": -1.5}, True),
+    "ratio_overflow_adv_zero": ({"old_logp": -200.0, "advantages": 0.0}, True),
+    "ratio_large_finite": ({"old_logp": -70.0}, True),
+    "adv_pinf": ({"advantages": _INF}, True),
+    "adv_ninf": ({"advantages": -_INF}, True),
+    "returns_inf": ({"returns": _INF}, True),
+    "value_inf": ({"value": _INF}, True),
+    "target_values_inf": ({"target_values": _INF}, True),
+    "kl_only": ({"old_sigma": 0.0}, True),
+}
+
+
+def _extreme_data(A, seed):
+    """the base minibatch of tests/test_ppo_gpu.py::test_fused_loss_propagates_nan_like_torch at B = XB, its rows moved off the loss's
+    branch points as _loss_data moves them"""
+    g = _gen(seed)
+    mk = lambda *s: torch.randn(*s, device=DEV, generator=g)
+    B = XB
+    d = dict(mu=mk(B, A) * 0.1, std=torch.full((A,), 0.3, device=DEV), value=mk(B, 1), actions=mk(B, A) * 0.3, old_logp=mk(B, 1) * 0.1 - 2,
+             old_mu=mk(B, A) * 0.1, old_sigma=torch.full((B, A), 0.3, device=DEV), advantages=mk(B, 1), returns=mk(B, 1), target_values=mk(B, 1))
+    ties = lambda: ppo_ref.loss_near_ties(d["mu"], d["std"], d["value"], d["actions"], d["old_logp"], d["returns"], d["target_values"], CLIP)
+    for _ in range(20):
+        bad = ties()
+        if not bool(bad.any()):
+            break
+        b = bad.reshape(-1, 1)
+        d["old_logp"] = torch.where(b, d["old_logp"] - 0.01, d["old_logp"])
+        d["target_values"] = torch.where(b, d["target_values"] + 0.013, d["target_values"])
+        d["returns"] = torch.where(b, d["returns"] + 0.011, d["returns"])
+    assert not bool(ties().any())
+    return d
+
+
+def _plant(d, plants, k):
+    """the planted copy of a minibatch: std[k], or rows XROWS (column k of a [B, A] tensor) of the named tensors"""
+    d = {n: t.clone() for n, t in d.items()}
+    for name, v in plants.items():
+        if name == "std":
+            d[name][k] = v
+        elif d[name].shape[1] == 1:
+            d[name][list(XROWS)] = v
+        else:
+            d[name][list(XROWS), k] = v
+    return d
+
+
+@pytest.mark.parametrize("case", list(EXTREMES))
+def test_loss_at_the_extremes_shows_what_torch_shows(case):
+    """grx_ppo_loss where sigma underflows or is invalid, the ratio overflows, and advantages, returns or values are infinite, B = 257,
+    A in {1, 10, 32}, the value loss clipped and not, against PPO's own fp32 torch spelling on the device (ppo_ref.TorchSpelling: underflow
+    and overflow are fp32 facts, float64 has no say in them).  ppo_ref.check_extremes: the loss and the mean KL are finite exactly when
+    torch's are and non-finite in the same way; a finite torch loss over a non-finite torch gradient finds the kernel's gradient non-finite
+    too (the step tail then skips the step); the non-finite masks of d_mu, d_value (per entry) and d_std (per action) are equal.  A planted
+    row does not leak: every other row of d_mu and d_value meets _check_loss's float64 bound.  The large finite ratio (exp(70 + logp)) is
+    an ordinary case for _check_loss.  No planted value had to be moved.  (Found by this: sigma_cube_underflow -- a finite loss, torch's
+    d_mu all NaN through `sigma = mean * 0.0 + std`, the kernel's d_mu finite; sigma_inf -- the same entries under a loss of -inf;
+    target_values_inf -- the kernel's d_value NaN (inf * 0) in the planted rows where clamp's backward selects 0.  Fixed in the kernel.)"""
+    plants, per_row = EXTREMES[case]
+    for A in (1, 10, 32):
+        base = _extreme_data(A, 7000 + A)
+        d = _plant(base, plants, A // 2)
+        for use_clipped in (True, False):
+            tag = (case, A, use_clipped)
+            if case == "ratio_large_finite":
+                lp = torch.distributions.Normal(d["mu"].double(), d["std"].double()).log_prob(d["actions"].double()).sum(-1)[list(XROWS)]
+                assert float(lp.max()) < 14.0 and float(lp.min()) > -60.0, (tag, lp.tolist())   # (1e4 > the ratio's distance to either end of fp32)
+                _check_loss(d, use_clipped, tag)
+                continue
+            want = ppo_ref.TorchSpelling(A, CLIP, VCOEF, ECOEF, use_clipped, DEV)(
+                d["mu"], d["std"], d["value"], d["actions"], d["old_logp"], d["old_mu"], d["old_sigma"], d["advantages"], d["returns"], d["target_values"])
+            got = _fused(d, use_clipped)
+            print(tag, "kernel", got[0].tolist(), "torch", want["out"].tolist(), "non-finite d_mu / d_std / d_value: kernel",
+                  [int((~torch.isfinite(x)).sum()) for x in got[1:]], "torch", [int((~torch.isfinite(want[n])).sum()) for n in ("d_mu", "d_std", "d_value")])
+            ppo_ref.check_extremes(got, want, tag)
+            if per_row:
+                rows = torch.ones(XB, dtype=torch.bool, device=DEV)
+                rows[list(XROWS)] = False
+                _check_loss(d, use_clipped, tag, rows=rows)
 
 
 # ---- grx_mlp_policy_head --------------------------------------------------------------------------------------------------------
@@ -257,10 +358,80 @@ TAIL_CASES = {
     "ceiling": (9e-4, 0.1 * DESIRED, 1, 0, False, 0.7, None),
     "nonfinite_loss": (1e-4, 3 * DESIRED, 1, 1000, True, float("nan"), None),
     "bad_flag": (1e-4, 0.3 * DESIRED, 1, 1000, True, 0.7, 1.0),
+    # a KL that is not finite: every comparison with NaN is false (the rate stays), +inf is above 2 * desired (down) -- as torch.where decides
+    "kl_nan": (1e-4, float("nan"), 1, 1000, True, 0.7, None),
+    "kl_inf": (1e-4, float("inf"), 1, 0, False, 0.7, None),
 }
+# One gradient element replaced after the clip threshold is chosen.  name: (value, place).  NaN, +-inf and 1e20 (finite; its square, 1e40,
+# is 30 times the largest float32) make the fp32 total norm non-finite: the step is skipped.  1e17 (square 1e34, 1 / 34000 of the largest
+# float32) is representable: the step runs, clipped by the usual rule.
+TAIL_POISON = {"nan": float("nan"), "pinf": float("inf"), "ninf": float("-inf"), "sq_overflow": 1e20}
+TAIL_POISON_SETS = ("edges", "full_body", "big")
+TAIL_LARGE = 1e17
 
 
-def _tail_state(numels, step0, seed):
+def _poison_index(numels, place):
+    """(tensor, element) of a poisoned-gradient place: `first` element 0 of tensor 0; `last` the last element of the last tensor; `ragged`
+    the last element (in the last, partial chunk of 4096) of the largest tensor but the last whose numel is no multiple of 4096; `global`
+    an element of the large tensor past 1024 chunks -- its partial is one tail_apply_kernel reads from global memory, not from LDS."""
+    if place == "first":
+        return 0, 0
+    if place == "last":
+        return len(numels) - 1, numels[-1] - 1
+    if place == "ragged":
+        t = max((i for i in range(len(numels) - 1) if numels[i] % 4096), key=lambda i: numels[i])
+        return t, numels[t] - 1
+    t = max(range(len(numels)), key=lambda i: numels[i])
+    assert place == "global" and numels[t] > 1025 * 4096 + 17
+    return t, 1025 * 4096 + 17
+
+
+def _tail_cases():
+    """(tset, case) of test_step_tail_matches_float64: every TAIL_CASES entry on every tensor set, then the poisoned and large gradients"""
+    pairs = [(tset, case) for tset in TAIL_SETS for case in TAIL_CASES]
+    for tset in TAIL_POISON_SETS:
+        places = ["first", "last", "ragged"] + (["global"] if tset == "big" else [])
+        pairs += [(tset, f"{name}@{place}@{step0}") for name in TAIL_POISON for place in places for step0 in (0, 1000)]
+        pairs += [(tset, f"large@ragged@{step0}") for step0 in (0, 1000)]
+    return pairs
+
+
+def _tail_case(case):
+    """(the TAIL_CASES tuple, poison) -- poison None or (value, place); a poisoned case: loss 0.7, no bad_flag, the clip on at step 0 and off at step 1000"""
+    if case in TAIL_CASES:
+        return TAIL_CASES[case], None
+    name, place, step0 = case.split("@")
+    step0 = int(step0)
+    return (1e-4, 3 * DESIRED if step0 else 0.3 * DESIRED, 1, step0, step0 == 0, 0.7, None), (TAIL_LARGE if name == "large" else TAIL_POISON[name], place)
+
+
+GUARD = 64                     # floats in front of and behind every tensor of the tail tests (256 bytes: the tensor's start keeps its alignment)
+SENTINEL_BITS = 0x4B3C614E     # what the guards of param, exp_avg and exp_avg_sq hold (the gradient's hold NaN)
+
+
+def _guarded(x, nan):
+    """`x` copied into the middle of a buffer with GUARD floats on either side: (the view, the buffer)"""
+    n = x.numel()
+    buf = torch.empty(n + 2 * GUARD, device=DEV)
+    if nan:
+        buf.fill_(float("nan"))
+    else:
+        buf.view(torch.int32).fill_(SENTINEL_BITS)
+    view = buf[GUARD:GUARD + n]
+    view.copy_(x)
+    assert view.data_ptr() % 256 == x.data_ptr() % 256 == 0
+    return view, buf
+
+
+def _guards_intact(buf):
+    b = buf.view(torch.int32)
+    return bool((b[:GUARD] == SENTINEL_BITS).all()) and bool((b[-GUARD:] == SENTINEL_BITS).all())
+
+
+def _tail_state(numels, step0, seed, guards=None):
+    """Parameters, gradients, both moments and step counters of a tensor set.  With `guards` (a list): every tensor sits inside a larger
+    buffer between two guard bands (_guarded), the gradients' NaN -- a read past either end of a gradient turns a step that must run into
+    a visible skip -- and the sentinel buffers of the other three are appended to `guards`."""
     g = _gen(seed)
     P = [torch.randn(n, device=DEV, generator=g) for n in numels]
     G = [torch.randn(n, device=DEV, generator=g) * (0.01 * (1 + i % 5)) for i, n in enumerate(numels)]
@@ -274,6 +445,12 @@ def _tail_state(numels, step0, seed):
         M = [torch.zeros(n, device=DEV) for n in numels]
         V = [torch.zeros(n, device=DEV) for n in numels]
     S = [torch.full((), float(step0), device=DEV) for _ in numels]
+    if guards is not None:
+        G = [_guarded(x, True)[0] for x in G]
+        for xs in (P, M, V):
+            for i, x in enumerate(xs):
+                xs[i], buf = _guarded(x, False)
+                guards.append(buf)
     return P, G, M, V, S
 
 
@@ -286,21 +463,37 @@ def _tail_structs(P, G, M, V, S, numels=None):
     return t
 
 
-@pytest.mark.parametrize("case", list(TAIL_CASES))
-@pytest.mark.parametrize("tset", list(TAIL_SETS))
+@pytest.mark.parametrize("tset,case", _tail_cases(), ids=[f"{t}-{c}" for t, c in _tail_cases()])
 def test_step_tail_matches_float64(tset, case):
     """grx_ppo_step_tail against ppo_ref.step_tail_ref (clip_grad_norm_ + Adam in float64) after the learning rate rule: the lr bit-equal
     to PPO._device_lr_update on the device, step counters exact, the clipped gradient's share of each moment within 4e-5 relative (the clip
     coefficient comes from an fp32 sum of squares over at most 1030 chunk partials: <= 1030 U32 relative, halved by the square root) plus
     a few roundings of both shares, parameters within 2 ulp plus 1e-4 of the update plus the moment tolerance carried through Adam's ratio.  A non-finite loss or bad_flag = 1
     leaves parameters, moments and step counters bit-identical and adds nothing to the statistics (the kernel multiplied the losses by 0
-    there, so a NaN value loss turned sums[0] into NaN: fixed).  `sums` gets sums[0] += value loss, sums[1] += surrogate, sums[2] = kl."""
+    there, so a NaN value loss turned sums[0] into NaN: fixed).  `sums` gets sums[0] += value loss, sums[1] += surrogate, sums[2] = kl.
+
+    So does a gradient whose fp32 total norm is not finite, under a finite loss (TAIL_POISON: one NaN, +inf, -inf or 1e20 element, in the
+    first and the last block, in a partial chunk, and in a chunk whose partial the second launch reads from global memory): the kernel
+    clamped fminf(max_norm / (NaN + 1e-6), 1) = 1 and ran Adam on the unclipped gradients, and an infinite norm's coefficient 0 put
+    inf * 0 = NaN into the moments.  One 1e17 element (TAIL_LARGE) is representable and must NOT skip: the same float64 comparison.
+    kl = NaN / +inf: the learning rate as torch.where decides it.
+
+    Every tensor lies between two guard bands of 64 floats inside its own allocation (_tail_state): the gradients' hold NaN, so a read
+    past either end makes a step that must run skip; the others hold a bit pattern that must still be there afterwards."""
     lib = fl.load_ppo_library()
-    lr0, kl, adaptive, step0, clip_on, loss, bad_flag = TAIL_CASES[case]
+    (lr0, kl, adaptive, step0, clip_on, loss, bad_flag), poison = _tail_case(case)
     numels = TAIL_SETS[tset]
-    P, G, M, V, S = _tail_state(numels, step0, len(case) * 31 + len(tset))
+    guards = []
+    P, G, M, V, S = _tail_state(numels, step0, len(case) * 31 + len(tset), guards)
+    if poison is not None and poison[0] == TAIL_LARGE:
+        ti, ei = _poison_index(numels, poison[1])
+        G[ti][ei] = TAIL_LARGE
+        poison = None
     total = math.sqrt(sum(float(x.double().pow(2).sum()) for x in G))
     max_norm = 0.5 * total if clip_on else 100.0 * total
+    if poison is not None:
+        ti, ei = _poison_index(numels, poison[1])
+        G[ti][ei] = poison[0]
     P0, M0, V0 = ([x.clone() for x in xs] for xs in (P, M, V))
     lr_t = torch.tensor(lr0, device=DEV)
     kl_t = torch.tensor(kl, device=DEV)
@@ -321,6 +514,7 @@ def test_step_tail_matches_float64(tset, case):
     a.beta1, a.beta2, a.eps = 0.9, 0.999, 1e-8
     assert lib.grx_ppo_step_tail(C.byref(t), C.byref(a), _stream()) == 0
     torch.cuda.synchronize()
+    assert all(_guards_intact(buf) for buf in guards), (tset, case, "a write outside a tensor")
 
     # the learning rate: bit-equal to the torch device rule, and to the fp32 restatement
     class _Alg:
@@ -337,15 +531,21 @@ def test_step_tail_matches_float64(tset, case):
     lr_used = float(lr_t)
 
     ref = ppo_ref.step_tail_ref(P0, G, M0, V0, [step0] * len(numels), lr_used, loss, bad_flag, np.float32(max_norm), 0.9, 0.999, 1e-8)
-    assert (ref["clip"] < 0.6) if clip_on else (ref["clip"] == 1.0)
+    if poison is None:
+        assert (ref["clip"] < 0.6) if clip_on else (ref["clip"] == 1.0)
+        assert ref["skipped"] == (case in ("nonfinite_loss", "bad_flag")), case
+    else:
+        assert ref["skipped"], case
     want_sums = sums.new_tensor([1.5, -0.25, 7.0])
     if not ref["skipped"]:
         want_sums[0] += vl_t; want_sums[1] += sl_t
     want_sums[2] = kl_t
-    assert torch.equal(sums, want_sums), (sums.tolist(), want_sums.tolist())
+    assert torch.equal(sums.view(torch.int32), want_sums.view(torch.int32)), (sums.tolist(), want_sums.tolist())   # (bits: kl may be NaN)
     if ref["skipped"]:
+        bits = lambda x: x.view(torch.int32)
         for i in range(len(numels)):
-            assert torch.equal(P[i], P0[i]) and torch.equal(M[i], M0[i]) and torch.equal(V[i], V0[i]) and float(S[i]) == step0, i
+            assert torch.equal(bits(P[i]), bits(P0[i])) and torch.equal(bits(M[i]), bits(M0[i])) and torch.equal(bits(V[i]), bits(V0[i])), (tset, case, i)
+            assert float(S[i]) == step0, (tset, case, i, float(S[i]))
         return
     for i in range(len(numels)):
         assert float(S[i]) == ref["steps"][i] == step0 + 1, i
@@ -551,6 +751,53 @@ def test_skipped_steps_leave_the_update_statistics_finite(path, monkeypatch):
         vl, sl = alg.update()
         assert vl == 0.0 and sl == 0.0, (path, vl, sl)
         assert all(torch.equal(p, b) for p, b in zip(ac.parameters(), before))
+    finally:
+        if path == "bucket":
+            dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("path", ["eager", "captured", "bucket", "fused"])
+def test_nonfinite_gradients_skip_every_step(path, monkeypatch):
+    """A finite loss over a non-finite gradient skips the step in every tail that clips.  `scalar` noise with sigma = 1e-18: every ratio
+    is exp(-1e36) = 0 and the loss finite, but d_std holds 0 * inf = NaN -- checked first on one minibatch through PPO._losses (on a copy
+    of the policy: the captured step wants parameters no eager backward has touched).  update() then leaves every parameter bit-identical
+    and the step counters where they were (0, or no optimizer state at all), and reports 0.0 for both mean losses.  The paths of
+    test_skipped_steps_leave_the_update_statistics_finite; before the norm joined the skip rule, torch's tails stepped on NaN gradients
+    (clip_grad_norm_ spreads the NaN norm over every .grad) and libgrx_ppo.so's clamped the coefficient to 1 and ran Adam."""
+    monkeypatch.setenv("GRX_PPO_FUSED_TAIL", "1" if path == "fused" else "0")
+    monkeypatch.setenv("GRX_PPO_GRAPH", "0" if path == "eager" else "1")
+    import torch.distributed as dist
+    if path == "bucket":
+        monkeypatch.setenv("GRX_PPO_FORCE_BUCKET", "1")
+        dist.init_process_group("nccl", init_method="tcp://127.0.0.1:29653", rank=0, world_size=1, device_id=torch.device("cuda", 0))
+    try:
+        torch.manual_seed(0)
+        ac = ActorCriticMLP(39, 168, 10, actor_hidden_dims=[64, 32], critic_hidden_dims=[64, 32], activation="elu", init_noise_std=1e-18)
+        kw = dict(num_learning_epochs=2, num_mini_batches=4, clip_param=CLIP, value_loss_coef=1.0, entropy_coef=0.01,
+                  use_clipped_value_loss=True, schedule="adaptive", desired_kl=0.01, device=DEV)
+        probe = PPO(copy.deepcopy(ac), **kw)
+        alg = PPO(ac, **kw)
+        assert alg._fused_tail == (path == "fused") and (alg._bucket is not None) == (path == "bucket")
+        alg.init_storage(256, 8)
+        st = alg.storage
+        g = _gen(3)
+        for t in (st.observations, st.pri_observations, st.actions, st.values, st.advantages, st.actions_log_prob, st.mu, st.returns):
+            t.copy_(torch.randn(t.shape, device=DEV, generator=g))
+        st.sigma.copy_(0.5 + torch.rand(st.sigma.shape, device=DEV, generator=g))
+        # the premise: a finite loss, a gradient that is not
+        batch = next(iter(st.mini_batch_generator(4, 1)))[:9]
+        with probe._blas_for_update():
+            _, _, loss, _ = probe._losses(*batch)
+            loss.backward()
+        std_grad = probe.actor_critic.std.grad
+        assert bool(torch.isfinite(loss)) and not bool(torch.isfinite(std_grad).all()), (float(loss), std_grad.tolist())
+        before = [p.detach().clone() for p in ac.parameters()]
+        vl, sl = alg.update()
+        bits = lambda x: x.detach().view(torch.int32)
+        assert all(torch.equal(bits(p), bits(b)) for p, b in zip(ac.parameters(), before)), path
+        steps = [float(alg.optimizer.state[p]["step"]) for p in ac.parameters() if "step" in alg.optimizer.state.get(p, {})]
+        assert all(s == 0.0 for s in steps), (path, steps)
+        assert vl == 0.0 and sl == 0.0, (path, vl, sl)
     finally:
         if path == "bucket":
             dist.destroy_process_group()

@@ -115,6 +115,47 @@ def test_tail_reference_matches_clip_grad_norm_and_adam(max_norm):
         assert r["skipped"] and r["steps"] == S and all(torch.equal(a, b) for a, b in zip(r["params"], P))
 
 
+@pytest.mark.parametrize("step0", [0, 1000])
+def test_tail_reference_skips_on_a_non_finite_gradient_norm(step0):
+    """step_tail_ref's skip rule under a finite loss: one NaN, +inf, -inf or 1e20 gradient element (the last: finite, its square above
+    the largest float32) gives `skipped` and untouched state; one 1e17 element (square 1e34: representable) does not skip and equals
+    float64 clip_grad_norm_ + torch.optim.Adam, clipping active and not."""
+    g = torch.Generator().manual_seed(17)
+    shapes = [(7, 5), (1,), (1030,), (3, 7)]
+    P = [torch.randn(*s, dtype=torch.float64, generator=g) for s in shapes]
+    M = [torch.randn(*s, dtype=torch.float64, generator=g) * 0.01 * bool(step0) for s in shapes]
+    V = [torch.rand(*s, dtype=torch.float64, generator=g) * 1e-4 * bool(step0) for s in shapes]
+    S = [float(step0)] * len(P)
+    grads = [torch.randn(*s, generator=g) * 0.1 for s in shapes]   # (fp32, as the kernel's)
+    for value in (float("nan"), float("inf"), float("-inf"), 1e20):
+        for t, e in ((0, 0), (2, 1029), (3, 20)):
+            G = [x.clone() for x in grads]
+            G[t].view(-1)[e] = value
+            r = ppo_ref.step_tail_ref(P, G, M, V, S, 3e-3, 0.7, None, 0.05, 0.9, 0.999, 1e-8)
+            assert r["skipped"] and r["steps"] == S, (value, t, e)
+            for new, old in ((r["params"], P), (r["exp_avg"], M), (r["exp_avg_sq"], V)):
+                assert all(torch.equal(a, b) for a, b in zip(new, old)), (value, t, e)
+    G = [x.clone() for x in grads]
+    G[2][517] = 1e17
+    for max_norm in (0.5e17, 1e19):
+        ps = [p.clone().requires_grad_() for p in P]
+        opt = torch.optim.Adam(ps, lr=3e-3, betas=(0.9, 0.999), eps=1e-8, foreach=False)
+        for p, gr, m, v in zip(ps, G, M, V):
+            opt.state[p] = {"step": torch.tensor(float(step0)), "exp_avg": m.clone(), "exp_avg_sq": v.clone()}
+            p.grad = gr.double()
+        total = torch.nn.utils.clip_grad_norm_(ps, max_norm, foreach=False)
+        opt.step()
+        r = ppo_ref.step_tail_ref(P, G, M, V, S, 3e-3, 0.7, None, max_norm, 0.9, 0.999, 1e-8)
+        assert not r["skipped"] and r["steps"] == [step0 + 1.0] * len(P)
+        assert r["clip"] < 0.6 if max_norm < 1e18 else r["clip"] == 1.0
+        assert abs(r["total"] - float(total)) <= 1e-12 * float(total)
+        for p, q, m, v in zip(ps, r["params"], r["exp_avg"], r["exp_avg_sq"]):
+            st = opt.state[p]
+            torch.testing.assert_close(q, p.detach(), rtol=1e-13, atol=1e-15)
+            torch.testing.assert_close(m, st["exp_avg"], rtol=1e-13, atol=1e-18)
+            torch.testing.assert_close(v, st["exp_avg_sq"], rtol=1e-13, atol=1e-20)
+
+
 def test_lr_rule_matches_the_device_update():
     """lr_rule_fp32 against PPO._device_lr_update on fp32 CPU tensors for every branch (down, up, keep, kl == 0, both clamps).  (On a
     HIP device torch divides by the host scalar 1.5 as a product with its fp32 reciprocal; the rule spells that product, so here the

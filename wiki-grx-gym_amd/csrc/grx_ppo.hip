@@ -64,8 +64,14 @@ __global__ __launch_bounds__(NTHR) void ppo_loss_kernel(int B, const float* __re
 #pragma unroll
         for (int k = 0; k < A; ++k) {
             const float s = sg[k], inv2 = 1.0f / (s * s);
-            d_mu[(size_t)i * A + k] = g_logp * df[k] * inv2;
-            red[3 + k] = g_logp * (df[k] * df[k] * inv2 / s - 1.0f / s);
+            // Where torch's d sigma is not finite, so are this row's d_mu and d_std: torch reaches sigma through var = sigma^2
+            // (num / (2 var) / (2 var) * 2 * 2 sigma: sigma = inf gives 0 * inf there), and update_distribution's sigma = mean * 0.0 + std
+            // hands the mean 0 * d sigma.  `np` is that chain times 0: +-0 where it is finite, NaN where it is not -- a finite loss must
+            // not hide a gradient torch shows as NaN (the step tail skips on a non-finite gradient norm).
+            const float half = 0.5f * inv2;
+            const float np = 0.f * (g_logp * (((df[k] * df[k] * half) * half) * 2.0f * (2.0f * s)) - g_logp / s);
+            d_mu[(size_t)i * A + k] = g_logp * df[k] * inv2 + np;
+            red[3 + k] = g_logp * (df[k] * df[k] * inv2 / s - 1.0f / s) + np;
         }
         const float v = value[i], ret = ret_[i];
         float vl, gv;
@@ -77,7 +83,8 @@ __global__ __launch_bounds__(NTHR) void ppo_loss_kernel(int B, const float* __re
             vl = nmax(l1, l2);
             const float u1 = l1 > l2 ? 1.f : (l1 == l2 ? 0.5f : 0.f), u2 = 1.f - u1;
             const float vin = (dv >= -clip && dv <= clip) ? 1.f : 0.f;
-            gv = u1 * 2.0f * (v - ret) + u2 * 2.0f * (vc - ret) * vin;
+            // (clamp's backward SELECTS: outside the interval the gradient is 0 even where (vc - ret) is infinite -- a target value of inf)
+            gv = u1 * 2.0f * (v - ret) + (vin != 0.f ? u2 * 2.0f * (vc - ret) : 0.f);
         } else {
             vl = (ret - v) * (ret - v);
             gv = -2.0f * (ret - v);
@@ -419,6 +426,7 @@ __global__ __launch_bounds__(TAIL_THR) void tail_norm_kernel(const grx_ppo_tail_
 }
 __global__ __launch_bounds__(TAIL_THR) void tail_apply_kernel(const grx_ppo_tail_tensors T, const grx_ppo_tail_args A, int nblocks) {
     __shared__ float s_clip;
+    __shared__ int s_skip;
     __shared__ float s_part[1024];
     const bool bad = tail_bad(A);
     for (int i = threadIdx.x; i < nblocks && i < 1024; i += TAIL_THR) s_part[i] = A.partials[i];   // (one parallel fetch; the sums below then run on LDS)
@@ -438,13 +446,21 @@ __global__ __launch_bounds__(TAIL_THR) void tail_apply_kernel(const grx_ppo_tail
         }
         const float total = sqrtf(tot);
         s_clip = fminf(A.max_grad_norm / (total + 1e-6f), 1.0f);
+        // a total norm that is not finite (a NaN or infinite gradient element, or an fp32 sum of squares that overflowed) skips the step
+        // like a non-finite loss: fminf(NaN, 1) = 1 would run Adam on the unclipped gradients, a clip of 0 would put inf * 0 into the moments
+        const bool skip = bad || !isfinite(total);
+        s_skip = skip;
         if (blockIdx.x == 0 && A.sums) {   // (a skipped step adds nothing: selected, not multiplied by 0 -- its losses may be NaN)
-            if (!bad) { A.sums[0] += *A.value_loss; A.sums[1] += *A.surrogate_loss; }
+            if (!skip) { A.sums[0] += *A.value_loss; A.sums[1] += *A.surrogate_loss; }
             A.sums[2] = *A.kl;
+        }
+        if (skip && !bad && blockIdx.x % TAIL_SPLIT == 0) {   // tail_norm_kernel counted this step before the norm was known: the block of a
+            const TailWhere w0 = tail_locate(T, blockIdx.x / TAIL_SPLIT);   // tensor's first sub-chunk takes it back (exact below 2^24 steps; no
+            if (w0.t >= 0 && w0.begin == 0) *T.step[w0.t] -= 1.f;           // block reads the counter on a skipped step)
         }
     }
     __syncthreads();
-    if (bad) return;
+    if (s_skip) return;
     TailWhere w = tail_locate(T, blockIdx.x / TAIL_SPLIT);
     if (w.t < 0) return;
     {   // this block's part of the chunk

@@ -47,7 +47,9 @@ __global__ __launch_bounds__(NTHR) void ppo_loss_sd_kernel(int B, const float* _
         for (int k = 0; k < A; ++k) {
             const float rs = raw[(size_t)i * (2 * A) + A + k], m = raw[(size_t)i * (2 * A) + k];
             const float s = log_std ? expf(rs) : rs;
-            const float ls = log_std ? rs : logf(s);   // (log: log sigma is s itself, not logf(expf(s)))
+            // (log: log sigma is s itself, not logf(expf(s)) -- unless expf saturated: torch's log of a sigma of inf or 0 is +-inf, and a
+            //  finite s = 100 there left the loss finite over gradients that are not)
+            const float ls = log_std ? ((s == INFINITY || s == 0.f) ? logf(s) : rs) : logf(s);
             sg[k] = s;
             df[k] = actions[(size_t)i * A + k] - m;
             // Normal.log_prob: -((x - loc)^2) / (2 var) - log(scale) - log(sqrt(2 pi))
@@ -72,7 +74,10 @@ __global__ __launch_bounds__(NTHR) void ppo_loss_sd_kernel(int B, const float* _
         for (int k = 0; k < A; ++k) {
             const float s = sg[k], inv2 = 1.0f / (s * s);
             d_raw[(size_t)i * (2 * A) + k] = g_logp * df[k] * inv2;
-            const float ds = g_logp * (df[k] * df[k] * inv2 / s - 1.0f / s) - g_ent / s;
+            // (np: torch's chain to d sigma through var = sigma^2, times 0 -- +-0 where it is finite, NaN where it is not: grx_ppo.hip)
+            const float half = 0.5f * inv2;
+            const float np = 0.f * (g_logp * (((df[k] * df[k] * half) * half) * 2.0f * (2.0f * s)) - g_logp / s);
+            const float ds = g_logp * (df[k] * df[k] * inv2 / s - 1.0f / s) - g_ent / s + np;
             d_raw[(size_t)i * (2 * A) + A + k] = log_std ? ds * s : ds;   // (log: d sigma / d s = sigma)
         }
         const float v = value[i], ret = ret_[i];
@@ -85,7 +90,8 @@ __global__ __launch_bounds__(NTHR) void ppo_loss_sd_kernel(int B, const float* _
             vl = nmax(l1, l2);
             const float u1 = l1 > l2 ? 1.f : (l1 == l2 ? 0.5f : 0.f), u2 = 1.f - u1;
             const float vin = (dv >= -clip && dv <= clip) ? 1.f : 0.f;
-            gv = u1 * 2.0f * (v - ret) + u2 * 2.0f * (vc - ret) * vin;
+            // (clamp's backward SELECTS: outside the interval the gradient is 0 even where (vc - ret) is infinite -- a target value of inf)
+            gv = u1 * 2.0f * (v - ret) + (vin != 0.f ? u2 * 2.0f * (vc - ret) : 0.f);
         } else {
             vl = (ret - v) * (ret - v);
             gv = -2.0f * (ret - v);

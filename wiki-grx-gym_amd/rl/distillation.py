@@ -361,7 +361,8 @@ class Distillation:
                 if not torch.isfinite(loss):
                     continue
                 loss.backward()
-                nn.utils.clip_grad_norm_(self._params, self.max_grad_norm)
+                if not torch.isfinite(nn.utils.clip_grad_norm_(self._params, self.max_grad_norm)):
+                    continue   # (a gradient whose norm is not finite skips the step too: include/grx_ppo.h grx_ppo_step_tail)
                 self.optimizer.step()
                 total += loss.item()
         return total / self.num_updates
@@ -402,10 +403,11 @@ class Distillation:
             if self._use_tail:
                 self._tail(loss, self._zero, loss, loss, sums, False, None, self.learning_rate, self.learning_rate, self.max_grad_norm)
                 return
-            bad = ~torch.isfinite(loss)
+        total_norm = nn.utils.clip_grad_norm_(self._params, self.max_grad_norm, foreach=True)
+        with torch.no_grad():   # (a gradient norm that is not finite skips the step as a non-finite loss does: the rule of grx_ppo_step_tail)
+            bad = ~torch.isfinite(loss) | ~torch.isfinite(total_norm)
             self.optimizer.found_inf = bad.float().reshape(())
             self.optimizer.grad_scale = None
-        nn.utils.clip_grad_norm_(self._params, self.max_grad_norm, foreach=True)
         self.optimizer.step()
         with torch.no_grad():
             sums[0] += torch.where(bad, 0.0, loss)   # (a skipped step adds nothing)

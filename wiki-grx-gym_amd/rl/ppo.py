@@ -495,7 +495,8 @@ class PPO:
                     self._apply_kl(kl_avg.item())
                 if bool(bad) or not bool(torch.isfinite(self._bucket[:self._nflat]).all()):
                     continue   # NaN-skip must be a collective decision: the averaged bucket is identical on every rank
-            nn.utils.clip_grad_norm_(ac.parameters(), self.max_grad_norm)
+            if not torch.isfinite(nn.utils.clip_grad_norm_(ac.parameters(), self.max_grad_norm)):
+                continue   # (a gradient whose norm is not finite skips the step too: include/grx_ppo.h grx_ppo_step_tail)
             self.optimizer.step()
             mean_value_loss += value_loss.item()
             mean_surrogate_loss += surrogate_loss.item()
@@ -524,7 +525,8 @@ class PPO:
                         continue
                     self.optimizer.zero_grad()
                     loss.backward()
-                    nn.utils.clip_grad_norm_(ac.parameters(), self.max_grad_norm)
+                    if not torch.isfinite(nn.utils.clip_grad_norm_(ac.parameters(), self.max_grad_norm)):
+                        continue   # (a gradient whose norm is not finite skips the step too: include/grx_ppo.h grx_ppo_step_tail)
                     self.optimizer.step()
                     sums[0] += value_loss.detach(); sums[1] += surrogate_loss.detach()
                     continue
@@ -534,11 +536,7 @@ class PPO:
                     continue
                 if adaptive:
                     self._device_lr_update(kl_mean)
-                with torch.no_grad():
-                    bad = ~torch.isfinite(loss)
-                    self.optimizer.found_inf = bad.float().reshape(())   # NaN-skip (ppo.py:297-299) through fused Adam's hook
-                    self.optimizer.grad_scale = None
-                nn.utils.clip_grad_norm_(ac.parameters(), self.max_grad_norm, foreach=True)
+                bad = self._clip_found_inf(~torch.isfinite(loss.detach()))
                 self.optimizer.step()
                 with torch.no_grad():
                     sums[0] += torch.where(bad, 0.0, value_loss.detach())   # (a skipped step adds nothing)
@@ -732,7 +730,8 @@ class PPO:
                     continue
                 self.optimizer.zero_grad()
                 loss.backward()
-                nn.utils.clip_grad_norm_(self.actor_critic.parameters(), self.max_grad_norm)
+                if not torch.isfinite(nn.utils.clip_grad_norm_(self.actor_critic.parameters(), self.max_grad_norm)):
+                    continue   # (a gradient whose norm is not finite skips the step too: include/grx_ppo.h grx_ppo_step_tail)
                 self.optimizer.step()
                 sums[0] += value_loss.detach(); sums[1] += surrogate_loss.detach()
         host = sums.tolist()
@@ -828,7 +827,8 @@ class PPO:
                     continue
                 self.optimizer.zero_grad()
                 loss.backward()
-                nn.utils.clip_grad_norm_(self.actor_critic.parameters(), self.max_grad_norm)
+                if not torch.isfinite(nn.utils.clip_grad_norm_(self.actor_critic.parameters(), self.max_grad_norm)):
+                    continue   # (a gradient whose norm is not finite skips the step too: include/grx_ppo.h grx_ppo_step_tail)
                 self.optimizer.step()
                 sums[0] += value_loss.detach(); sums[1] += surrogate_loss.detach()
         host = sums.tolist()
@@ -862,12 +862,7 @@ class PPO:
                 continue
             if adaptive:
                 self._device_lr_update(kl_mean)
-            with torch.no_grad():
-                # NaN-skip (ppo.py:297-299) without a sync: the fused Adam kernel leaves parameters and moments
-                # untouched when found_inf is set (the GradScaler hook)
-                self.optimizer.found_inf = bad.float().reshape(())
-                self.optimizer.grad_scale = None
-            nn.utils.clip_grad_norm_(ac.parameters(), self.max_grad_norm, foreach=True)
+            bad = self._clip_found_inf(bad)
             self.optimizer.step()
             with torch.no_grad():
                 sums[0] += torch.where(bad, 0.0, value_loss.detach())   # (a skipped step adds nothing, also when its losses are NaN: NaN * 0 is NaN)
@@ -897,16 +892,24 @@ class PPO:
             return
         if adaptive:
             self._device_lr_update(kl_mean)
-        with torch.no_grad():
-            bad = ~torch.isfinite(loss)
-            self.optimizer.found_inf = bad.float().reshape(())   # NaN-skip (ppo.py:297-299) through fused Adam's hook
-            self.optimizer.grad_scale = None
-        nn.utils.clip_grad_norm_(self.actor_critic.parameters(), self.max_grad_norm, foreach=True)
+        bad = self._clip_found_inf(~torch.isfinite(loss.detach()))
         self.optimizer.step()
         with torch.no_grad():
             sums[0] += torch.where(bad, 0.0, value_loss.detach())   # (a skipped step adds nothing, also when its losses are NaN: NaN * 0 is NaN)
             sums[1] += torch.where(bad, 0.0, surrogate_loss.detach())
             sums[2] = kl_mean
+
+    def _clip_found_inf(self, bad):
+        """clip_grad_norm_, then the NaN-skip (ppo.py:297-299) without a sync: the fused Adam kernel leaves parameters, moments and step
+        counters untouched when found_inf is set (the GradScaler hook).  A step is skipped when `bad` (a non-finite loss) or when the
+        gradients' total norm, which clip_grad_norm_ returns, is not finite -- the rule of grx_ppo_step_tail (include/grx_ppo.h) and of the
+        multi-rank paths; torch alone would step on NaN or zeroed gradients there.  Returns the decision, for the statistics."""
+        total_norm = nn.utils.clip_grad_norm_(self.actor_critic.parameters(), self.max_grad_norm, foreach=True)
+        with torch.no_grad():
+            bad = bad | ~torch.isfinite(total_norm)
+            self.optimizer.found_inf = bad.float().reshape(())
+            self.optimizer.grad_scale = None
+        return bad
 
     def _step_tail(self, loss, kl_mean, value_loss, surrogate_loss, sums, adaptive, bad_flag=None):
         """Adaptive learning rate, NaN-skip, clip_grad_norm_, Adam.step() and the update's statistics through libgrx_ppo.so (two launches);
