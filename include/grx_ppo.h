@@ -280,4 +280,7 @@ int grx_rnd_reward(int N, int E, const float* pred, const float* targ, float gam
 /* ... and the action-smoothness regulariser: the minibatch with its successor and perturbed rows, and the two smoothness
  * losses, csrc/grx_ppo_smooth.hip in the same library */
 #include "grx_ppo_smooth.h"
+/* ... and the concurrent state estimator: its rollout forward -- copy, every layer, column select -- in one launch,
+ * csrc/grx_ppo_est.hip in the same library */
+#include "grx_ppo_est.h"
 #endif

@@ -100,6 +100,9 @@ def load_ppo_library():
         lib.grx_smooth_loss_partials_size.argtypes = [C.c_int, C.c_int]
         lib.grx_smooth_loss.restype = C.c_int
         lib.grx_smooth_loss.argtypes = [C.c_int, C.c_int, fp, C.c_int, C.c_int, fp, C.c_float, C.c_float, fp, fp, fp, C.c_void_p]
+        # the concurrent state estimator's rollout forward (rl/estimator.py)
+        lib.grx_est_forward.restype = C.c_int
+        lib.grx_est_forward.argtypes = [fp, C.c_int, C.c_int, fp, C.c_int, fp, C.POINTER(C.c_int), fp, fp, C.c_void_p]
         _LIB = lib
     return _LIB
 

@@ -109,6 +109,11 @@ class OnPolicyRunner:
         self.smooth = self.algorithm_cfg.get("smooth") or None
         if self.smooth is not None:
             self._check_smooth()
+        # a concurrent state estimator: a small network regresses privileged columns from the actor's input, its output is
+        # appended to that input, and it is trained on the rollout after PPO's update.  Not config keys either (`--estimator` /
+        # `--estimator_*` or assignments to train_cfg.runner set them): without `estimator` nothing of rl/estimator.py is constructed
+        self.estimator = None
+        estimator_cfg = self._check_estimator(env) if bool(self.cfg.get("estimator", False)) else None
         if self.distill_from is not None:
             teacher = self._check_distillation(env, device)
         self.obs_history = self.critic_obs_history = None
@@ -137,7 +142,9 @@ class OnPolicyRunner:
                                  "loss": self.algorithm.loss_type}
             self._alt_inputs = self._distill_inputs
         else:
-            actor_critic = policy_cls(actor_in, critic_in, env.num_actions, **self.policy_cfg).to(device)
+            # (with an estimator the policy acts on [x | est(x)]: E more columns; the normaliser's statistics stay actor_in wide)
+            policy_in = actor_in + (len(estimator_cfg["cols"]) if estimator_cfg is not None else 0)
+            actor_critic = policy_cls(policy_in, critic_in, env.num_actions, **self.policy_cfg).to(device)
             extra = {}
             if self.symmetry is not None:   # (a model the joint map refuses, an asymmetric height scan: build_maps' ValueError)
                 from .symmetry import build_maps
@@ -152,6 +159,11 @@ class OnPolicyRunner:
                 self.rnd = self.algorithm.rnd = RandomNetworkDistillation(
                     env.num_pri_obs if state == "privileged" else env.num_obs, env.num_envs, self.cfg["num_steps_per_env"], device,
                     **rnd_cfg)
+            if estimator_cfg is not None:   # (after the policy and RND, as RND after the policy)
+                from .estimator import StateEstimator
+                self.estimator = StateEstimator(actor_in, env.num_obs, env.num_pri_obs, env.num_envs, self.cfg["num_steps_per_env"], device,
+                                                targets=estimator_cfg["targets"], hidden_dims=estimator_cfg["hidden_dims"],
+                                                learning_rate=estimator_cfg["learning_rate"], num_epochs=estimator_cfg["num_epochs"])
         self.alg = self.algorithm
         self.num_steps_per_env, self.save_interval = self.cfg["num_steps_per_env"], self.cfg["save_interval"]
         # exact resume: every save() also writes train_state_<it>.pt, the whole training state; not a config key
@@ -220,6 +232,8 @@ class OnPolicyRunner:
             else:
                 critic_obs = obs_n
             obs = obs_n
+        if self.estimator is not None:   # the last stage: [x | est(x)]; the frame's targets wait for the row's rollout step
+            obs = self.estimator.step(obs, pri.to(self.device), None)
         alg.actor_critic.train()
         ep_infos = []
         if pending is None:
@@ -242,6 +256,8 @@ class OnPolicyRunner:
             if self.rnd is not None:
                 self.rnd.iteration = it
             with torch.inference_mode():
+                if self.estimator is not None:   # the row this rollout starts with was built from the frames parked last
+                    self.estimator.begin_rollout()
                 for t_ in range(self.num_steps_per_env):
                     actions = alg.act(obs, critic_obs)
                     obs, pri, rewards, dones, infos = env.step(actions)
@@ -255,6 +271,8 @@ class OnPolicyRunner:
                         obs, critic_obs = self._stack_history(obs, critic_obs if pri is not None else None, dones)
                     if self.empirical_normalization and self._alt_inputs is None:
                         obs, critic_obs = self._normalize_step(obs, critic_obs if pri is not None else None)
+                    if self.estimator is not None:   # this row is acted on at step t_ + 1: its targets are the raw privileged frame of this step
+                        obs = self.estimator.step(obs, pri.to(self.device), t_ + 1 if t_ + 1 < self.num_steps_per_env else None)
                     if self.log_dir is not None:
                         if "episode" in infos:
                             ep_infos.append(infos["episode"])
@@ -282,6 +300,8 @@ class OnPolicyRunner:
                 mean_rnd_loss = self.rnd.update(alg.num_learning_epochs, alg.num_mini_batches)
                 if self.log_dir is not None and self.is_main:
                     mean_intrinsic_reward = self.rnd.intrinsic.mean().item()
+            if self.estimator is not None:   # the regression on this rollout: the stored rows' first columns against the stored targets
+                mean_estimator_loss = self.estimator.update(alg.storage.observations, alg.num_mini_batches)
             alg.clear_storage()
             if self.sync_timers:
                 torch.cuda.synchronize()
@@ -412,6 +432,27 @@ class OnPolicyRunner:
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise NotImplementedError("--rnd with a world size above 1 is not implemented: the return statistics are per process")
 
+    def _check_estimator(self, env):
+        """what --estimator does not combine with; returns its options: targets, their columns, hidden_dims, learning_rate, num_epochs"""
+        from .estimator import check_hidden_dims, check_layout, parse_targets, target_columns
+        if self.recurrent:
+            raise ValueError("--estimator and --recurrent exclude each other: the memory is the estimator")
+        if self.privileged_actor:
+            raise ValueError("--estimator and --privileged_actor exclude each other: the actor already reads the targets")
+        if self.distill_from is not None:
+            raise ValueError("--estimator and --distill_from exclude each other: a distillation run has no PPO update the estimator trains beside")
+        if self.symmetry is not None:
+            raise ValueError("--estimator and --symmetry exclude each other: a mirror map of the appended columns is not implemented")
+        if bool(self.cfg.get("exact_resume", False)):
+            raise NotImplementedError("--estimator with --exact_resume: the estimator's state is not part of train_state_<it>.pt")
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("--estimator with a world size above 1 is not implemented: it trains in one process only")
+        check_layout(env)
+        targets = parse_targets(self.cfg.get("estimator_targets", "lin_vel"))
+        return {"targets": targets, "cols": target_columns(targets, env.num_obs),
+                "hidden_dims": check_hidden_dims(self.cfg.get("estimator_hidden_dims", (128, 64))),
+                "learning_rate": float(self.cfg.get("estimator_learning_rate", 1e-3)), "num_epochs": int(self.cfg.get("estimator_num_epochs", 1))}
+
     def _check_noise(self):
         """what --noise_std_type log / --state_dependent_std do not combine with"""
         from .modules import NOISE_STD_TYPES
@@ -499,6 +540,8 @@ class OnPolicyRunner:
                 w.add_scalar("Loss/rnd", locs["mean_rnd_loss"], it)
                 w.add_scalar("Train/mean_intrinsic_reward", locs["mean_intrinsic_reward"], it)
                 w.add_scalar("Train/rnd_weight", self.rnd.weight(it), it)
+            if self.estimator is not None:
+                w.add_scalar("Loss/estimator", locs["mean_estimator_loss"], it)
         w.add_scalar("Perf/total_fps", fps, it)
         w.add_scalar("Perf/collection time", locs["collection_time"], it)
         w.add_scalar("Perf/learning_time", locs["learn_time"], it)
@@ -551,6 +594,8 @@ class OnPolicyRunner:
             saved["noise"] = dict(self.noise)
         if self.rnd is not None:   # (likewise): both networks, RND's normaliser, the discounted-return state, the optimizer, the configuration
             saved["rnd"] = self.rnd.checkpoint()
+        if self.estimator is not None:   # (likewise): the network, its optimizer, the targets and hidden layers
+            saved["estimator"] = self.estimator.checkpoint()
         torch.save(saved, path)
         if self.exact_resume:
             torch.save(self._train_state(), train_state_path(path))
@@ -633,6 +678,14 @@ class OnPolicyRunner:
                              f"the one that was trained (pass --noise_std_type {want['std_type']}"
                              f"{' --state_dependent_std' if want['state_dependent'] else ' without --state_dependent_std'}, or set "
                              "train_cfg.policy.noise_std_type / train_cfg.policy.state_dependent_std, to match the checkpoint)")
+        mine = dict(self.estimator.config) if self.estimator is not None else None
+        theirs = dict(loaded["estimator"]["config"]) if "estimator" in loaded else None
+        if theirs != mine:
+            want = ("--estimator --estimator_targets " + ",".join(theirs["targets"]) + " --estimator_hidden_dims "
+                    + " ".join(str(h) for h in theirs["hidden_dims"])) if theirs is not None else "no --estimator"
+            raise ValueError(f"{path} was saved with estimator={theirs}, this runner has estimator={mine}: the policy's inputs would not be "
+                             f"what it was trained on (pass {want}, or set train_cfg.runner.estimator / estimator_targets / "
+                             "estimator_hidden_dims, to match the checkpoint)")
         saved_hist = loaded.get("obs_history", {"actor": 1, "critic": 1})   # (a checkpoint without the key: no history)
         if "distillation" in loaded and self.distillation is None:
             return self._load_student(path, loaded, saved_hist)
@@ -658,6 +711,8 @@ class OnPolicyRunner:
             print(f"{path} holds no rnd entry: random network distillation starts fresh")
         elif "rnd" in loaded:
             print(f"{path} holds an rnd entry, this runner has no --rnd: ignored")
+        if self.estimator is not None:
+            self.estimator.load_checkpoint(loaded["estimator"], load_optimizer)
         self.current_learning_iteration = loaded["iter"]
         return loaded["infos"]
 
@@ -719,6 +774,16 @@ class OnPolicyRunner:
                 self.critic_obs_normalizer.eval()
                 inner = NormalizedPolicy(inner, self.critic_obs_normalizer)
             return HistoryPolicy(inner, self.env.num_pri_obs, self.critic_obs_history_length).to(device if device is not None else self.device)
+        if self.estimator is not None:   # raw SINGLE frames in: history, the statistics as they are now, then [x | est(x)] into the actor
+            from .estimator import EstimatorPolicy
+            self.estimator.net.eval()
+            inner = EstimatorPolicy(self._mean_actor(), self.estimator.net)
+            if self.empirical_normalization:
+                self.obs_normalizer.eval()
+                inner = NormalizedPolicy(inner, self.obs_normalizer)
+            if self.obs_history_length > 1:
+                inner = HistoryPolicy(inner, self.env.num_obs, self.obs_history_length)
+            return inner.to(device if device is not None else self.device)
         if self.empirical_normalization:   # raw observations in, as in training: normalised with the statistics as they are
             norm, act = self.obs_normalizer, self.algorithm.actor_critic.act_inference
             norm.eval()

@@ -74,7 +74,8 @@ def play(args, steps=None, log_root="default"):
         exported = export_policy_as_jit(ppo_runner.algorithm.actor_critic, out_dir,
                                         normalizer=(ppo_runner.critic_obs_normalizer if privileged else ppo_runner.obs_normalizer)
                                         if ppo_runner.empirical_normalization else None,
-                                        history=ppo_runner.critic_obs_history_length if privileged else ppo_runner.obs_history_length)
+                                        history=ppo_runner.critic_obs_history_length if privileged else ppo_runner.obs_history_length,
+                                        estimator=ppo_runner.estimator.net if getattr(ppo_runner, "estimator", None) is not None else None)
         print(f"EXPORT_POLICY: Exported policy as jit script to: {exported}")
     os.makedirs(out_dir, exist_ok=True)
 

@@ -99,6 +99,17 @@ def get_args(argv=None):
                    help="The frame --rnd's networks read: the env's privileged frame (no observation noise) or the actor's raw frame")
     p.add_argument("--rnd_num_outputs", type=int, default=32, help="Width of --rnd's embedding (1..256)")
     p.add_argument("--rnd_learning_rate", type=float, default=1e-3, help="Learning rate of --rnd's predictor (fixed)")
+    p.add_argument("--estimator", action="store_true", default=False,
+                   help="A concurrently trained state estimator: a small network regresses privileged quantities from the actor's input and "
+                        "its output is appended to that input (saved in the checkpoint; play needs the same flag, targets and hidden dims)")
+    p.add_argument("--estimator_targets", type=str, default="lin_vel",
+                   help="What --estimator regresses: a comma-separated subset of lin_vel (3 columns), base_height (1), feet_contact (2), "
+                        "feet_height (2) (default lin_vel, not tuned)")
+    p.add_argument("--estimator_hidden_dims", type=int, nargs="+", default=[128, 64],
+                   help="Hidden layers of --estimator's network: 1 to 3 widths of 1..256 (default 128 64, not tuned)")
+    p.add_argument("--estimator_learning_rate", type=float, default=1e-3, help="Learning rate of --estimator's network (fixed; default 1e-3, not tuned)")
+    p.add_argument("--estimator_num_epochs", type=int, default=1,
+                   help="Passes of --estimator's regression over a rollout, in PPO's num_mini_batches minibatches (default 1, not tuned)")
     p.add_argument("--noise_std_type", type=str, choices=["scalar", "log"],
                    help="The action noise's parameter: std itself (scalar, default) or log_std with sigma = exp(log_std), which cannot reach "
                         "zero (saved in the checkpoint; play needs the same value)")
@@ -173,6 +184,13 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
             a.rnd_start_it, a.rnd_end_it, a.rnd_at_it = (int(getattr(args, k, 0)) for k in ("rnd_start_it", "rnd_end_it", "rnd_at_it"))
             a.rnd_state, a.rnd_num_outputs = getattr(args, "rnd_state", "privileged"), int(getattr(args, "rnd_num_outputs", 32))
             a.rnd_learning_rate = float(getattr(args, "rnd_learning_rate", 1e-3))
+        if getattr(args, "estimator", False):   # (likewise; the --estimator_* values travel only with --estimator)
+            r = cfg_train.runner
+            r.estimator = True
+            r.estimator_targets = getattr(args, "estimator_targets", "lin_vel")
+            r.estimator_hidden_dims = [int(h) for h in getattr(args, "estimator_hidden_dims", [128, 64])]
+            r.estimator_learning_rate = float(getattr(args, "estimator_learning_rate", 1e-3))
+            r.estimator_num_epochs = int(getattr(args, "estimator_num_epochs", 1))
         if getattr(args, "recurrent", False):   # (likewise: the policy config has no rnn_hidden_size otherwise)
             cfg_train.runner.policy_class_name = "ActorCriticRecurrent"
             cfg_train.policy.rnn_hidden_size = int(getattr(args, "rnn_hidden_size", 256))
@@ -213,13 +231,15 @@ def get_load_path(root, load_run=-1, checkpoint=-1):
     return os.path.join(load_run, model)
 
 
-def export_policy_as_jit(actor_critic, path, normalizer=None, history=1):
+def export_policy_as_jit(actor_critic, path, normalizer=None, history=1, estimator=None):
     """A recurrent actor_critic (rl.recurrent.ActorCriticRecurrent): the exported module is an nn.LSTM with its state in buffers in front
     of the actor's layers (rl.recurrent.ExportedRecurrentPolicy: one raw frame per call, `reset_memory()` and `reset(dones)` exported).
     `normalizer` (an rl.normalizer.EmpiricalNormalization): the exported module takes RAW observations and normalises them itself.
     `history` > 1 (the runner's obs_history_length): it takes raw SINGLE frames and keeps the last `history` of them itself
     (rl.history.HistoryPolicy: `reset_memory()` and `reset(dones)` are exported methods).
-    An actor_critic with `state_dependent_std`: the exported module returns the mean, the first A of the actor's 2A outputs"""
+    An actor_critic with `state_dependent_std`: the exported module returns the mean, the first A of the actor's 2A outputs.
+    `estimator` (the network of an rl.estimator.StateEstimator): behind history and normaliser the module appends the estimate to the
+    actor's input itself (rl.estimator.EstimatorPolicy); a consumer still feeds raw single frames"""
     os.makedirs(path, exist_ok=True)
     path = os.path.join(path, "policy_jit.pt")
     if getattr(actor_critic, "is_recurrent", False):
@@ -229,12 +249,17 @@ def export_policy_as_jit(actor_critic, path, normalizer=None, history=1):
     # (state_dependent_std: the actor's output layer is [mean | s]; the exported module slices, a consumer sees [B, A] as ever)
     inner = actor_critic.inference_actor() if hasattr(actor_critic, "inference_actor") else actor_critic.actor
     model = copy.deepcopy(inner).to("cpu")
+    appended = 0
+    if estimator is not None:
+        from ..rl.estimator import EstimatorPolicy
+        model = EstimatorPolicy(model, copy.deepcopy(estimator).to("cpu"))
+        appended = estimator.output_size
     if normalizer is not None:
         from ..rl.normalizer import NormalizedPolicy
         model = NormalizedPolicy(model, copy.deepcopy(normalizer).to("cpu"))
     if history > 1:
         from ..rl.history import HistoryPolicy
-        stacked = actor_critic.actor.model[0].in_features
+        stacked = actor_critic.actor.model[0].in_features - appended
         if stacked % history:
             raise ValueError(f"export_policy_as_jit: the actor takes {stacked} inputs, no multiple of history={history}")
         model = HistoryPolicy(model, stacked // history, history)
