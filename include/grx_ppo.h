@@ -283,4 +283,7 @@ int grx_rnd_reward(int N, int E, const float* pred, const float* targ, float gam
 /* ... and the concurrent state estimator: its rollout forward -- copy, every layer, column select -- in one launch,
  * csrc/grx_ppo_est.hip in the same library */
 #include "grx_ppo_est.h"
+/* ... and value normalisation: the GAE scan, the advantages' normalisation and the returns' running statistics in three
+ * launches, csrc/grx_ppo_gae.hip in the same library */
+#include "grx_ppo_gae.h"
 #endif

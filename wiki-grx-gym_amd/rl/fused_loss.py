@@ -103,6 +103,11 @@ def load_ppo_library():
         # the concurrent state estimator's rollout forward (rl/estimator.py)
         lib.grx_est_forward.restype = C.c_int
         lib.grx_est_forward.argtypes = [fp, C.c_int, C.c_int, fp, C.c_int, fp, C.POINTER(C.c_int), fp, fp, C.c_void_p]
+        # the GAE scan with value normalisation (rl/value_norm.py)
+        lib.grx_gae_partials_size.restype = C.c_int
+        lib.grx_gae_partials_size.argtypes = [C.c_int, C.c_int]
+        lib.grx_gae_returns.restype = C.c_int
+        lib.grx_gae_returns.argtypes = [C.c_int, C.c_int] + [fp] * 4 + [C.c_float] * 3 + [fp] * 10 + [C.c_void_p]
         _LIB = lib
     return _LIB
 

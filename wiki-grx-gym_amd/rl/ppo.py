@@ -68,7 +68,8 @@ class PPO:
                  value_loss_coef=1.0, entropy_coef=0.0, learning_rate=1e-3, learning_rate_min=1e-5, learning_rate_max=1e-2,
                  weight_decay=0.0, max_grad_norm=1.0, use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01,
                  device="cpu", storage_class="RolloutStorage", precision="fp32", symmetry=None, symmetry_coef=1.0, symmetry_maps=None,
-                 smooth=None, smooth_temporal_coef=0.1, smooth_spatial_coef=0.1, smooth_sigma=0.05, **kwargs):
+                 smooth=None, smooth_temporal_coef=0.1, smooth_spatial_coef=0.1, smooth_sigma=0.05, value_norm=None, value_norm_eps=1e-5,
+                 **kwargs):
         if kwargs:
             print("PPO.__init__ got unexpected arguments, which will be ignored: " + str(list(kwargs)))
         # precision="bf16": every hidden layer of actor and critic multiplies bf16 operands into fp32 accumulators -- in the rollout's
@@ -164,6 +165,12 @@ class PPO:
             self._init_smooth(smooth, smooth_temporal_coef, smooth_spatial_coef, smooth_sigma)
         # random network distillation (rl/rnd.py): the runner builds it under `--rnd` and assigns it; None runs nothing of it
         self.rnd = None
+        # value normalisation (rl/value_norm.py): the critic's output is a normalised value, denormalised wherever the rollout
+        # uses it; the statistics follow the rollout's returns once per iteration ("popart": the critic's output layer follows them too).  Not
+        # a config key: `--value_norm` or an assignment to train_cfg.algorithm sets it; None imports nothing of it
+        self.value_norm = None
+        if value_norm is not None:
+            self._init_value_norm(value_norm, value_norm_eps)
         self.num_updates = 0
         self._params = [p for p in self.actor_critic.parameters() if p.requires_grad]
         n = sum(p.numel() for p in self._params)
@@ -204,6 +211,17 @@ class PPO:
         # the nine minibatch tensors (obs, cobs, actions, values, advantages, returns, old_logp, old_mu, old_sigma): how each gets its second half
         self._sym_modes = [2, 2, 2, 1, 1, 1, 1, 2, 2] if symmetry in ("augment", "both") else [2, 0, 0, 0, 0, 0, 0, 0, 0]
         self._sym_tensor_maps = [maps.obs, maps.cobs, maps.actions, None, None, None, None, maps.actions, maps.sigma]
+
+    def _init_value_norm(self, mode, eps):
+        if self._recurrent:
+            raise ValueError("PPO: --value_norm and --recurrent exclude each other: denormalising a recurrent critic's rollout and bootstrap "
+                             "values is not implemented")
+        if _world() > 1:
+            raise NotImplementedError("PPO: --value_norm with a world size above 1 is not implemented: the return statistics are per process")
+        from .value_norm import ValueNormalizer, output_layer
+        self.value_norm = ValueNormalizer(mode, eps, self.device)
+        if mode == "popart":
+            output_layer(self.actor_critic.critic)   # (raises on a critic whose output layer cannot be rescaled)
 
     def _init_smooth(self, smooth, coef_t, coef_s, sigma):
         from .smooth import blocks, check_values
@@ -251,6 +269,8 @@ class PPO:
         else:
             actions = ac.act(actor_observations).detach()
         values = ac.evaluate(critic_observations).detach()
+        if self.value_norm is not None:   # (the network's output is a normalised value: the storage and GAE work in reward units)
+            values = self.value_norm.denormalize(values)
         logp = ac.get_actions_log_prob(actions).detach()
         return actions, values, logp, ac.action_mean.detach(), ac.action_std.detach()
 
@@ -306,9 +326,10 @@ class PPO:
                     return actions, ac.get_actions_log_prob(actions).detach(), ac.action_mean.detach(), ac.action_std.detach()
 
                 def critic_part():
-                    if fuse:
-                        return mlp_forward(ac.critic, self._act_in[1])
-                    return ac.evaluate(self._act_in[1]).detach()
+                    v = mlp_forward(ac.critic, self._act_in[1]) if fuse else ac.evaluate(self._act_in[1]).detach()
+                    if self.value_norm is not None:   # (captured: a replay reads the statistics' tensors, so it sees them as they are then)
+                        v = self.value_norm.denormalize(v)
+                    return v
                 side = torch.cuda.Stream(device=self.device)
                 self._act_side = torch.cuda.Stream(device=self.device)
                 side.wait_stream(cur)
@@ -402,6 +423,10 @@ class PPO:
             self.storage.compute_returns(last_values, self.gamma, self.lam)
             return
         last_values = self.actor_critic.evaluate(last_critic_obs).detach()
+        if self.value_norm is not None:   # GAE in reward units, the statistics' update, then the storage's values / returns normalised in place
+            self.value_norm.compute_returns(self.storage, self.value_norm.denormalize(last_values), self.gamma, self.lam,
+                                            critic=self.actor_critic.critic)
+            return
         self.storage.compute_returns(last_values, self.gamma, self.lam)
 
     def update_learning_rate(self, kl_mean):

@@ -112,6 +112,15 @@ class OnPolicyRunner:
         # a concurrent state estimator: a small network regresses privileged columns from the actor's input, its output is
         # appended to that input, and it is trained on the rollout after PPO's update.  Not config keys either (`--estimator` /
         # `--estimator_*` or assignments to train_cfg.runner set them): without `estimator` nothing of rl/estimator.py is constructed
+        # value normalisation: the critic learns a normalised value, the statistics follow the rollout's returns.  Not a config
+        # key either (`--value_norm` or an assignment to train_cfg.algorithm sets it): without it nothing of rl/value_norm.py is imported.
+        # inference_only (scripts/play.py sets it): load() takes the actor from a checkpoint whatever its value_norm entry says
+        self.value_norm = self.algorithm_cfg.get("value_norm") or None
+        self.inference_only = bool(self.cfg.get("inference_only", False))
+        if self.value_norm is not None:
+            self._check_value_norm()
+        else:
+            self.algorithm_cfg = {k: v for k, v in self.algorithm_cfg.items() if k not in ("value_norm", "value_norm_eps")}
         self.estimator = None
         estimator_cfg = self._check_estimator(env) if bool(self.cfg.get("estimator", False)) else None
         if self.distill_from is not None:
@@ -417,6 +426,21 @@ class OnPolicyRunner:
             raise ValueError(f"--smooth {self.smooth} with num_steps_per_env={self.cfg['num_steps_per_env']}: a rollout of one step holds no "
                              "successor row (use --smooth spatial or a longer rollout)")
 
+    def _check_value_norm(self):
+        """what --value_norm does not combine with"""
+        modes = ("running", "popart")   # (rl.value_norm.MODES)
+        if self.value_norm not in modes:
+            raise ValueError(f"--value_norm must be one of {modes}, not {self.value_norm!r}")
+        if self.recurrent:
+            raise ValueError("--value_norm and --recurrent exclude each other: denormalising a recurrent critic's rollout and bootstrap values "
+                             "is not implemented")
+        if self.distill_from is not None:
+            raise ValueError("--value_norm and --distill_from exclude each other: a distillation run has no critic whose target could be normalised")
+        if bool(self.cfg.get("exact_resume", False)):
+            raise NotImplementedError("--value_norm with --exact_resume: the return statistics are not part of train_state_<it>.pt")
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("--value_norm with a world size above 1 is not implemented: the return statistics are per process")
+
     def _check_rnd(self, env, rnd_cfg):
         """what --rnd does not combine with"""
         from .rnd import STATES
@@ -542,6 +566,9 @@ class OnPolicyRunner:
                 w.add_scalar("Train/rnd_weight", self.rnd.weight(it), it)
             if self.estimator is not None:
                 w.add_scalar("Loss/estimator", locs["mean_estimator_loss"], it)
+            if self.value_norm is not None:   # (Loss/value_function above is in normalised units then)
+                w.add_scalar("Train/value_norm_mean", alg.value_norm.mean.item(), it)
+                w.add_scalar("Train/value_norm_std", alg.value_norm.std.item(), it)
         w.add_scalar("Perf/total_fps", fps, it)
         w.add_scalar("Perf/collection time", locs["collection_time"], it)
         w.add_scalar("Perf/learning_time", locs["learn_time"], it)
@@ -596,6 +623,8 @@ class OnPolicyRunner:
             saved["rnd"] = self.rnd.checkpoint()
         if self.estimator is not None:   # (likewise): the network, its optimizer, the targets and hidden layers
             saved["estimator"] = self.estimator.checkpoint()
+        if self.value_norm is not None:   # (likewise): the mode, eps and the five statistics
+            saved["value_norm"] = self.algorithm.value_norm.checkpoint()
         torch.save(saved, path)
         if self.exact_resume:
             torch.save(self._train_state(), train_state_path(path))
@@ -686,6 +715,13 @@ class OnPolicyRunner:
             raise ValueError(f"{path} was saved with estimator={theirs}, this runner has estimator={mine}: the policy's inputs would not be "
                              f"what it was trained on (pass {want}, or set train_cfg.runner.estimator / estimator_targets / "
                              "estimator_hidden_dims, to match the checkpoint)")
+        if not self.inference_only:   # (play.py and the exported policy use the actor only)
+            theirs = loaded["value_norm"]["mode"] if "value_norm" in loaded else None
+            if theirs != self.value_norm:
+                want = f"--value_norm {theirs}" if theirs is not None else "no --value_norm"
+                raise ValueError(f"{path} was saved with value_norm={theirs!r}, this runner has value_norm={self.value_norm!r}: the critic's "
+                                 f"output would not be in the units it was trained in (pass {want}, or set train_cfg.algorithm.value_norm, to "
+                                 "match the checkpoint)")
         saved_hist = loaded.get("obs_history", {"actor": 1, "critic": 1})   # (a checkpoint without the key: no history)
         if "distillation" in loaded and self.distillation is None:
             return self._load_student(path, loaded, saved_hist)
@@ -713,6 +749,8 @@ class OnPolicyRunner:
             print(f"{path} holds an rnd entry, this runner has no --rnd: ignored")
         if self.estimator is not None:
             self.estimator.load_checkpoint(loaded["estimator"], load_optimizer)
+        if self.value_norm is not None and "value_norm" in loaded and loaded["value_norm"]["mode"] == self.value_norm:
+            self.algorithm.value_norm.load_checkpoint(loaded["value_norm"])
         self.current_learning_iteration = loaded["iter"]
         return loaded["infos"]
 

@@ -61,6 +61,7 @@ def play(args, steps=None, log_root="default"):
     obs = env.get_observations()
 
     train_cfg.runner.resume = True
+    train_cfg.runner.inference_only = True   # (the actor alone is used: a checkpoint's value_norm entry is ignored)
     ppo_runner, train_cfg = task_registry.make_alg_runner(env=env, name=args.task, args=args, train_cfg=train_cfg, log_root=log_root)
     policy = ppo_runner.get_inference_policy(device=env.device)
     privileged = getattr(ppo_runner, "privileged_actor", False)   # (a teacher trained with --privileged_actor acts on the privileged frames)

@@ -85,6 +85,10 @@ def get_args(argv=None):
     p.add_argument("--smooth_spatial_coef", type=float, default=0.1, help="Weight of --smooth's spatial term (default 0.1, not tuned)")
     p.add_argument("--smooth_sigma", type=float, default=0.05,
                    help="Standard deviation of --smooth's perturbation of the actor's (stacked, normalised) input (default 0.05, not tuned)")
+    p.add_argument("--value_norm", type=str, choices=["running", "popart"],
+                   help="Value normalisation: the critic learns returns normalised by their running mean / std (running), and its output "
+                        "layer is rescaled when the statistics move, so that its predictions are preserved (popart); saved in the checkpoint, "
+                        "--resume needs the same value")
     p.add_argument("--rnd", action="store_true", default=False,
                    help="Random network distillation: an intrinsic reward (predictor error against a fixed random network) added to the env's")
     p.add_argument("--rnd_weight", type=float, default=0.1, help="Weight of --rnd's intrinsic reward (default 0.1, not tuned)")
@@ -175,6 +179,8 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
             a.smooth_temporal_coef = float(getattr(args, "smooth_temporal_coef", 0.1))
             a.smooth_spatial_coef = float(getattr(args, "smooth_spatial_coef", 0.1))
             a.smooth_sigma = float(getattr(args, "smooth_sigma", 0.05))
+        if getattr(args, "value_norm", None) is not None:   # (likewise)
+            cfg_train.algorithm.value_norm = args.value_norm
         if getattr(args, "rnd", False):   # (likewise; the --rnd_* values travel only with --rnd)
             a = cfg_train.algorithm
             a.rnd = True
