@@ -286,4 +286,7 @@ int grx_rnd_reward(int N, int E, const float* pred, const float* targ, float gam
 /* ... and value normalisation: the GAE scan, the advantages' normalisation and the returns' running statistics in three
  * launches, csrc/grx_ppo_gae.hip in the same library */
 #include "grx_ppo_gae.h"
+/* ... and the Lipschitz gradient penalty: the element-wise passes of the penalty and of its second-order backward,
+ * csrc/grx_ppo_gp.hip in the same library */
+#include "grx_ppo_gp.h"
 #endif

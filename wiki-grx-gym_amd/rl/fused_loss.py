@@ -108,6 +108,19 @@ def load_ppo_library():
         lib.grx_gae_partials_size.argtypes = [C.c_int, C.c_int]
         lib.grx_gae_returns.restype = C.c_int
         lib.grx_gae_returns.argtypes = [C.c_int, C.c_int] + [fp] * 4 + [C.c_float] * 3 + [fp] * 10 + [C.c_void_p]
+        # the Lipschitz gradient penalty's element-wise passes (rl/grad_penalty.py)
+        lib.grx_gp_seed.restype = C.c_int
+        lib.grx_gp_seed.argtypes = [C.c_int, C.c_int] + [fp] * 4 + [C.c_void_p]
+        lib.grx_gp_gate.restype = C.c_int
+        lib.grx_gp_gate.argtypes = [C.c_int, C.c_int] + [fp] * 3 + [C.c_void_p]
+        lib.grx_gp_sqnorm_partials_size.restype = C.c_int
+        lib.grx_gp_sqnorm_partials_size.argtypes = [C.c_int, C.c_int]
+        lib.grx_gp_sqnorm.restype = C.c_int
+        lib.grx_gp_sqnorm.argtypes = [C.c_int, C.c_int] + [fp] * 3 + [C.c_void_p]
+        lib.grx_gp_gate_backward.restype = C.c_int
+        lib.grx_gp_gate_backward.argtypes = [C.c_int, C.c_int] + [fp] * 8 + [C.c_void_p]
+        lib.grx_gp_seed_backward.restype = C.c_int
+        lib.grx_gp_seed_backward.argtypes = [C.c_int, C.c_int] + [fp] * 8 + [C.c_void_p]
         _LIB = lib
     return _LIB
 

@@ -69,7 +69,7 @@ class PPO:
                  weight_decay=0.0, max_grad_norm=1.0, use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01,
                  device="cpu", storage_class="RolloutStorage", precision="fp32", symmetry=None, symmetry_coef=1.0, symmetry_maps=None,
                  smooth=None, smooth_temporal_coef=0.1, smooth_spatial_coef=0.1, smooth_sigma=0.05, value_norm=None, value_norm_eps=1e-5,
-                 **kwargs):
+                 grad_penalty_coef=None, **kwargs):
         if kwargs:
             print("PPO.__init__ got unexpected arguments, which will be ignored: " + str(list(kwargs)))
         # precision="bf16": every hidden layer of actor and critic multiplies bf16 operands into fp32 accumulators -- in the rollout's
@@ -171,6 +171,12 @@ class PPO:
         self.value_norm = None
         if value_norm is not None:
             self._init_value_norm(value_norm, value_norm_eps)
+        # the Lipschitz gradient penalty (rl/grad_penalty.py): grad_penalty_coef * mean_r ||d logp_r / d x_r||^2 joins the loss,
+        # its second-order pass written out by hand and sharing the actor's one backward.  Not a config key: `--grad_penalty_coef` or an
+        # assignment to train_cfg.algorithm sets it; None imports nothing of it
+        self.grad_penalty_coef, self.mean_grad_penalty = None, 0.0
+        if grad_penalty_coef is not None:
+            self._init_grad_penalty(grad_penalty_coef)
         self.num_updates = 0
         self._params = [p for p in self.actor_critic.parameters() if p.requires_grad]
         n = sum(p.numel() for p in self._params)
@@ -222,6 +228,26 @@ class PPO:
         self.value_norm = ValueNormalizer(mode, eps, self.device)
         if mode == "popart":
             output_layer(self.actor_critic.critic)   # (raises on a critic whose output layer cannot be rescaled)
+
+    def _init_grad_penalty(self, coef):
+        from .grad_penalty import check_coef, linears_of
+        why = "the penalty's second-order pass covers the plain fp32 MLP actor on one minibatch of stored rows"
+        if self._recurrent:
+            raise ValueError(f"PPO: --grad_penalty_coef and --recurrent exclude each other: {why}")
+        if self.symmetry is not None:
+            raise ValueError(f"PPO: --grad_penalty_coef and --symmetry exclude each other: {why}")
+        if self.smooth is not None:
+            raise ValueError(f"PPO: --grad_penalty_coef and --smooth exclude each other: {why}")
+        if self._state_dependent:
+            raise ValueError(f"PPO: --grad_penalty_coef and --state_dependent_std exclude each other: {why}, with one sigma per action")
+        if self.precision == "bf16":
+            raise ValueError(f"PPO: --grad_penalty_coef and --precision bf16 exclude each other: {why}")
+        if _world() > 1:
+            raise NotImplementedError("PPO: --grad_penalty_coef with a world size above 1 is not implemented: it trains in one process only")
+        coef = check_coef(coef)
+        linears_of(self.actor_critic.actor)   # (raises on an actor the pass does not cover)
+        self.grad_penalty_coef = coef
+        self._gp_sum = torch.zeros(1, device=self.device)   # the update's sum of P (finite steps), read back once per update
 
     def _init_smooth(self, smooth, coef_t, coef_s, sigma):
         from .smooth import blocks, check_values
@@ -472,6 +498,8 @@ class PPO:
             return self._update_symmetry()
         if self.smooth is not None:
             return self._update_smooth()
+        if self.grad_penalty_coef is not None:
+            return self._update_gp()
         if self._device_lr:
             # For these GEMM shapes (batch ~10^4 rows, 39..512 columns, fp32) rocBLAS's kernel choices beat hipBLASLt's by 2x
             # on the weight-gradient products dY^T X (27-48 us against 66-73 us, tools/gpu_gemm_probe.py).  torch's BLAS
@@ -596,14 +624,20 @@ class PPO:
         ac = self.actor_critic
         return self._fused_loss and not ac.fixed_std and ac.num_actor_output <= 32   # the kernel's action-count limit
 
-    def _forward(self, obs, cobs):
-        """(mu, value): the actor's and the critic's forward of one minibatch (state_dependent_std: mu is the actor's raw [mean | s])"""
+    def _forward(self, obs, cobs, actor=None):
+        """(mu, value): the actor's and the critic's forward of one minibatch (state_dependent_std: mu is the actor's raw [mean | s]).
+        actor: what runs in the actor's place and whose result is handed back as mu (the gradient penalty's function)"""
         ac = self.actor_critic
-        if self._state_dependent and not self._loss_is_fused():
+        if actor is not None:
+            if not self._loss_is_fused():
+                return actor(obs), ac.evaluate(cobs)
+        elif self._state_dependent and not self._loss_is_fused():
             return ac.actor(obs), ac.evaluate(cobs)   # (the raw output [mean | s]: _loss_terms splits it)
-        if not self._loss_is_fused():
+        elif not self._loss_is_fused():
             ac.update_distribution(obs)   # (the torch spelling in _loss_terms reads sigma from the distribution)
             return ac.action_mean, ac.evaluate(cobs)
+        else:
+            actor = ac.actor
         # (only while the actor's GEMMs go to rocBLAS -- update() / _build_graph's preference: with torch's default hipBLASLt on BOTH
         #  streams, the value head's weight gradient at minibatch 49152 came out wrong once and the step did not finish twice)
         if self._two_streams and torch.backends.cuda.preferred_blas_library() == torch._C._BlasBackend.Cublas:
@@ -615,11 +649,11 @@ class PPO:
             self._aux_stream.wait_stream(cur)
             with torch.cuda.stream(self._aux_stream):
                 value = ac.evaluate(cobs)
-            mu = ac.actor(obs)
+            mu = actor(obs)
             cur.wait_stream(self._aux_stream)
             value.record_stream(cur)
             return mu, value
-        mu = ac.actor(obs)
+        mu = actor(obs)
         return mu, ac.evaluate(cobs)
 
     def _loss_terms(self, mu, value, actions, target_values, advantages, returns, old_logp, old_mu, old_sigma):
@@ -862,15 +896,74 @@ class PPO:
             self.learning_rate = float(self._lr_t.item())
         return host[0] / self.num_updates, host[1] / self.num_updates
 
+    # ------------------------------------------------------------------ the Lipschitz gradient penalty (rl/grad_penalty.py)
+    def _losses_gp(self, obs, cobs, actions, target_values, advantages, returns, old_logp, old_mu, old_sigma):
+        """_losses with the actor run by rl.grad_penalty.GradPenalty: mu bit-equal to the actor's own, P = mean_r ||d logp_r / d obs_r||^2 of
+        the stored actions beside it, and grad_penalty_coef * P joins the loss.  The PPO gradient arriving at mu and the penalty's gradient
+        go down the actor in that function's one backward."""
+        from .grad_penalty import grad_penalty
+        ac = self.actor_critic
+        sigma = _noise_std(ac)
+        pen = []
+
+        def actor(x):
+            mu, P = grad_penalty(ac.actor, x, actions, sigma)
+            pen.append(P)
+            return mu
+        mu, value = self._forward(obs, cobs, actor=actor)
+        if not self._loss_is_fused():   # (the torch spelling in _loss_terms reads sigma from the distribution)
+            ac.distribution = torch.distributions.Normal(mu, mu * 0.0 + sigma, validate_args=False)
+        surrogate_loss, value_loss, loss, kl_mean = self._loss_terms(mu, value, actions, target_values, advantages, returns,
+                                                                     old_logp, old_mu, old_sigma)
+        loss = loss + self.grad_penalty_coef * pen[0]
+        with torch.no_grad():   # (a step the NaN-skip drops adds nothing, as with the other statistics)
+            P = pen[0].detach().reshape(1)
+            self._gp_sum += torch.where(torch.isfinite(loss.detach()).reshape(1), P, torch.zeros_like(P))
+        return surrogate_loss, value_loss, loss, kl_mean
+
+    def _update_gp(self):
+        """update() with the gradient penalty on: the captured step, the eager device one or the CPU one below, on the plain minibatch"""
+        self._gp_sum.zero_()
+        if self._device_lr:
+            with self._blas_for_update():
+                out = self._update_graphed() if self._use_graph else self._update_device()
+        else:
+            out = self._update_gp_cpu()
+        self.mean_grad_penalty = float(self._gp_sum.item()) / self.num_updates   # one extra 4-byte read-back per update
+        return out
+
+    def _update_gp_cpu(self):
+        """update()'s CPU loop -- host-side adaptive learning rate, NaN-skip, clip and Adam -- around _losses_gp"""
+        adaptive = self.desired_kl is not None and self.schedule == "adaptive"
+        mean_value_loss, mean_surrogate_loss = 0.0, 0.0
+        for (obs, cobs, actions, target_values, advantages, returns, old_logp, old_mu, old_sigma, _, _) in \
+                self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs):
+            surrogate_loss, value_loss, loss, kl_mean = self._losses_gp(obs, cobs, actions, target_values, advantages, returns,
+                                                                        old_logp, old_mu, old_sigma)
+            if adaptive:
+                self._apply_kl(kl_mean.item())
+            if not torch.isfinite(loss):
+                continue
+            self.optimizer.zero_grad()
+            loss.backward()
+            if not torch.isfinite(nn.utils.clip_grad_norm_(self.actor_critic.parameters(), self.max_grad_norm)):
+                continue   # (a gradient whose norm is not finite skips the step too: include/grx_ppo.h grx_ppo_step_tail)
+            self.optimizer.step()
+            mean_value_loss += value_loss.item()
+            mean_surrogate_loss += surrogate_loss.item()
+        self.num_updates = self.num_learning_epochs * self.num_mini_batches
+        return mean_value_loss / self.num_updates, mean_surrogate_loss / self.num_updates
+
     def _update_device(self):
         """Same arithmetic as update(), no host round-trips inside the minibatch loop."""
         ac, multi = self.actor_critic, _collective_path()
         adaptive = self.desired_kl is not None and self.schedule == "adaptive"
         sums = torch.zeros(3, device=self.device)        # value loss, surrogate loss, last KL
+        losses = self._losses if self.grad_penalty_coef is None else self._losses_gp
         for (obs, cobs, actions, target_values, advantages, returns, old_logp, old_mu, old_sigma, _, _) in \
                 self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs):
-            surrogate_loss, value_loss, loss, kl_mean = self._losses(obs, cobs, actions, target_values, advantages, returns,
-                                                                      old_logp, old_mu, old_sigma)
+            surrogate_loss, value_loss, loss, kl_mean = losses(obs, cobs, actions, target_values, advantages, returns,
+                                                               old_logp, old_mu, old_sigma)
             if multi:
                 self._zero_flat_grads()
             else:
@@ -907,6 +1000,8 @@ class PPO:
         losses = self._losses if self.symmetry is None else self._losses_sym
         if self.smooth is not None:   # (the actor's input has R mb rows; the pairs' valid bytes are a static buffer beside the batch)
             losses = self._losses_smooth
+        if self.grad_penalty_coef is not None:   # (the same nine tensors: the penalty reads the actor's input and the stored actions)
+            losses = self._losses_gp
         surrogate_loss, value_loss, loss, kl_mean = losses(obs, cobs, actions, target_values, advantages, returns,
                                                            old_logp, old_mu, old_sigma)
         # grads dropped, not zero-filled: backward then WRITES each .grad (from the graph's private pool on replay) instead of
@@ -1089,6 +1184,8 @@ class PPO:
             self._sym_sum.zero_()   # (the dry runs of a capture added to it)
         if self.smooth is not None:
             self._smooth_sum.zero_()   # (likewise)
+        if self.grad_penalty_coef is not None:
+            self._gp_sum.zero_()   # (likewise)
         multi = _collective_path()
         gather = None
         if self._fused_store:   # (libgrx_ppo.so is in use)

@@ -121,6 +121,12 @@ class OnPolicyRunner:
             self._check_value_norm()
         else:
             self.algorithm_cfg = {k: v for k, v in self.algorithm_cfg.items() if k not in ("value_norm", "value_norm_eps")}
+        # the Lipschitz gradient penalty: grad_penalty_coef * mean ||d logp / d obs||^2 in PPO's loss.  Not a config key either
+        # (`--grad_penalty_coef` or an assignment to train_cfg.algorithm sets it): without it nothing of rl/grad_penalty.py is imported;
+        # nothing of it is saved
+        self.grad_penalty_coef = self.algorithm_cfg.get("grad_penalty_coef")
+        if self.grad_penalty_coef is not None:
+            self._check_grad_penalty()
         self.estimator = None
         estimator_cfg = self._check_estimator(env) if bool(self.cfg.get("estimator", False)) else None
         if self.distill_from is not None:
@@ -426,6 +432,29 @@ class OnPolicyRunner:
             raise ValueError(f"--smooth {self.smooth} with num_steps_per_env={self.cfg['num_steps_per_env']}: a rollout of one step holds no "
                              "successor row (use --smooth spatial or a longer rollout)")
 
+    def _check_grad_penalty(self):
+        """what --grad_penalty_coef does not combine with"""
+        from .grad_penalty import check_coef
+        why = "the penalty's second-order pass covers the plain fp32 MLP actor on one minibatch of stored rows"
+        if self.recurrent:
+            raise ValueError(f"--grad_penalty_coef and --recurrent exclude each other: {why}")
+        if self.symmetry is not None:
+            raise ValueError(f"--grad_penalty_coef and --symmetry exclude each other: {why}")
+        if self.smooth is not None:
+            raise ValueError(f"--grad_penalty_coef and --smooth exclude each other: {why}")
+        if self.state_dependent_std:
+            raise ValueError(f"--grad_penalty_coef and --state_dependent_std exclude each other: {why}, with one sigma per action")
+        if self.distill_from is not None:
+            raise ValueError("--grad_penalty_coef and --distill_from exclude each other: a distillation run has no PPO loss to add to")
+        if self.algorithm_cfg.get("precision", "fp32") == "bf16":
+            raise ValueError(f"--grad_penalty_coef and --precision bf16 exclude each other: {why}")
+        if bool(self.cfg.get("exact_resume", False)):
+            raise NotImplementedError("--grad_penalty_coef with --exact_resume is not implemented: a resumed run with the penalty is not pinned "
+                                      "bit for bit")
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("--grad_penalty_coef with a world size above 1 is not implemented: it trains in one process only")
+        check_coef(self.grad_penalty_coef, who="runner")
+
     def _check_value_norm(self):
         """what --value_norm does not combine with"""
         modes = ("running", "popart")   # (rl.value_norm.MODES)
@@ -560,6 +589,8 @@ class OnPolicyRunner:
             if self.smooth is not None:
                 w.add_scalar("Loss/smooth_temporal", alg.mean_smooth_temporal, it)
                 w.add_scalar("Loss/smooth_spatial", alg.mean_smooth_spatial, it)
+            if self.grad_penalty_coef is not None:
+                w.add_scalar("Loss/grad_penalty", alg.mean_grad_penalty, it)
             if self.rnd is not None:
                 w.add_scalar("Loss/rnd", locs["mean_rnd_loss"], it)
                 w.add_scalar("Train/mean_intrinsic_reward", locs["mean_intrinsic_reward"], it)

@@ -8,6 +8,7 @@
     python -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless --smooth both --smooth_sigma 0.05           (action-smoothness regularisation, CAPS: DESIGN.md 4.14)
     python -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless --estimator --estimator_targets lin_vel,base_height   (a concurrent state estimator: DESIGN.md 4.15)
     python -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless --value_norm popart                    (value normalisation, running or PopArt: DESIGN.md 4.16)
+    python -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless --grad_penalty_coef 0.002              (a Lipschitz gradient penalty on the policy: DESIGN.md 4.17)
     torchrun --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless
 """
 import os

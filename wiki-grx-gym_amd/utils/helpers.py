@@ -85,6 +85,9 @@ def get_args(argv=None):
     p.add_argument("--smooth_spatial_coef", type=float, default=0.1, help="Weight of --smooth's spatial term (default 0.1, not tuned)")
     p.add_argument("--smooth_sigma", type=float, default=0.05,
                    help="Standard deviation of --smooth's perturbation of the actor's (stacked, normalised) input (default 0.05, not tuned)")
+    p.add_argument("--grad_penalty_coef", type=float,
+                   help="Lipschitz gradient penalty (Chen et al., 2024) in PPO's update: this weight times the batch mean of "
+                        "||d log pi(a|s) / d s||^2 joins the loss (a float > 0; the paper uses 0.002, not tuned here); nothing is saved")
     p.add_argument("--value_norm", type=str, choices=["running", "popart"],
                    help="Value normalisation: the critic learns returns normalised by their running mean / std (running), and its output "
                         "layer is rescaled when the statistics move, so that its predictions are preserved (popart); saved in the checkpoint, "
@@ -179,6 +182,8 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
             a.smooth_temporal_coef = float(getattr(args, "smooth_temporal_coef", 0.1))
             a.smooth_spatial_coef = float(getattr(args, "smooth_spatial_coef", 0.1))
             a.smooth_sigma = float(getattr(args, "smooth_sigma", 0.05))
+        if getattr(args, "grad_penalty_coef", None) is not None:   # (likewise)
+            cfg_train.algorithm.grad_penalty_coef = float(args.grad_penalty_coef)
         if getattr(args, "value_norm", None) is not None:   # (likewise)
             cfg_train.algorithm.value_norm = args.value_norm
         if getattr(args, "rnd", False):   # (likewise; the --rnd_* values travel only with --rnd)
