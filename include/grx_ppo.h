@@ -289,4 +289,7 @@ int grx_rnd_reward(int N, int E, const float* pred, const float* targ, float gam
 /* ... and the Lipschitz gradient penalty: the element-wise passes of the penalty and of its second-order backward,
  * csrc/grx_ppo_gp.hip in the same library */
 #include "grx_ppo_gp.h"
+/* ... and layer normalisation in the hidden layers: LayerNorm + ELU behind a layer's product, forward and backward,
+ * csrc/grx_ppo_ln.hip in the same library */
+#include "grx_ppo_ln.h"
 #endif

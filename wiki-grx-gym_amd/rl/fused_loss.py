@@ -121,6 +121,13 @@ def load_ppo_library():
         lib.grx_gp_gate_backward.argtypes = [C.c_int, C.c_int] + [fp] * 8 + [C.c_void_p]
         lib.grx_gp_seed_backward.restype = C.c_int
         lib.grx_gp_seed_backward.argtypes = [C.c_int, C.c_int] + [fp] * 8 + [C.c_void_p]
+        # LayerNorm + ELU behind a hidden layer's product (rl/modules.py _TrainLinearLNELU)
+        lib.grx_ln_elu_forward.restype = C.c_int
+        lib.grx_ln_elu_forward.argtypes = [C.c_int, C.c_int, fp, fp, fp, C.c_float, fp, fp, fp, C.c_void_p]
+        lib.grx_ln_elu_backward_partials_size.restype = C.c_int
+        lib.grx_ln_elu_backward_partials_size.argtypes = [C.c_int, C.c_int]
+        lib.grx_ln_elu_backward.restype = C.c_int
+        lib.grx_ln_elu_backward.argtypes = [C.c_int, C.c_int] + [fp] * 11 + [C.c_void_p]
         _LIB = lib
     return _LIB
 
@@ -365,8 +372,79 @@ def _linears_of(mlp):
     return lin if len(mods) % 2 == 1 else None
 
 
+LN_MAX_COLS = 1024   # include/grx_ppo_ln.h GRX_LN_MAX_COLS
+
+
+def ln_fused():
+    """False under GRX_LN_FUSED=0: a LayerNorm hidden layer runs its torch spelling (rl/modules.py _TrainLinearLNELU), nothing of it is fused"""
+    return os.environ.get("GRX_LN_FUSED", "1") != "0"
+
+
+def _layers_of(mlp):
+    """(weight, bias, norm) of every nn.Linear of an rl.modules.MLP -- norm the nn.LayerNorm behind a hidden layer, or None -- if it is
+    Linear -> [LayerNorm ->] ELU(1) -> ... -> Linear, else None.  (_linears_of keeps refusing a LayerNorm network: bf16, the gradient
+    penalty and the estimator's fused forward do not cover it.)"""
+    mods = list(mlp.model)
+    layers, i = [], 0
+    while i < len(mods):
+        m = mods[i]
+        if not isinstance(m, torch.nn.Linear):
+            return None
+        if i + 1 == len(mods):
+            layers.append((m.weight, m.bias, None))
+            return layers
+        norm = None
+        if isinstance(mods[i + 1], torch.nn.LayerNorm):
+            norm = mods[i + 1]
+            if not (norm.elementwise_affine and norm.bias is not None and tuple(norm.normalized_shape) == (m.out_features,)
+                    and m.out_features <= LN_MAX_COLS):
+                return None
+            i += 1
+        if not (i + 1 < len(mods) and isinstance(mods[i + 1], torch.nn.ELU) and mods[i + 1].alpha == 1.0):
+            return None
+        layers.append((m.weight, m.bias, norm))
+        i += 2
+    return None   # (no output layer behind the last activation)
+
+
 def mlp_can_fuse(mlp, x):
-    return x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and _linears_of(mlp) is not None
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2):
+        return False
+    layers = _layers_of(mlp)
+    return layers is not None and (ln_fused() or all(n is None for _, _, n in layers))
+
+
+def ln_elu_forward(z, gamma, beta, eps, stats=True):
+    """(y, mean, rstd) = ELU(LayerNorm(z)) per row through grx_ln_elu_forward (one launch); stats=False (inference): (y, None, None)"""
+    lib = load_ppo_library()
+    z = _f32c(z)
+    rows, cols = z.shape
+    y = torch.empty_like(z)
+    mean, rstd = (torch.empty(rows, device=z.device, dtype=torch.float32) for _ in range(2)) if stats else (None, None)
+    with torch.cuda.device(z.device):
+        rc = lib.grx_ln_elu_forward(rows, cols, z.data_ptr(), _f32c(gamma).data_ptr(), _f32c(beta).data_ptr(), float(eps), y.data_ptr(),
+                                    mean.data_ptr() if stats else None, rstd.data_ptr() if stats else None,
+                                    C.c_void_p(torch.cuda.current_stream(z.device).cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"grx_ln_elu_forward failed ({rc}): {rows} x {cols}")
+    return y, mean, rstd
+
+
+def ln_elu_backward(dy, y, z, mean, rstd, gamma):
+    """(dz, dgamma, dbeta, dbias) of ELU(LayerNorm(z)) through grx_ln_elu_backward: three launches, the column sums in grx_ppo_colsum's order"""
+    lib = load_ppo_library()
+    dy, y, z, gamma = _f32c(dy), _f32c(y), _f32c(z), _f32c(gamma)
+    rows, cols = dy.shape
+    dz = torch.empty_like(dy)
+    dgamma, dbeta, dbias = (torch.empty(cols, device=dy.device, dtype=torch.float32) for _ in range(3))
+    partials = torch.empty(max(1, lib.grx_ln_elu_backward_partials_size(rows, cols)), device=dy.device, dtype=torch.float32)
+    with torch.cuda.device(dy.device):
+        rc = lib.grx_ln_elu_backward(rows, cols, dy.data_ptr(), y.data_ptr(), z.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(),
+                                     dz.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), dbias.data_ptr(), partials.data_ptr(),
+                                     C.c_void_p(torch.cuda.current_stream(dy.device).cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"grx_ln_elu_backward failed ({rc}): {rows} x {cols}")
+    return dz, dgamma, dbeta, dbias
 
 
 def _layer(lib, x, w, b, elu, stream, bf16=False):
@@ -375,6 +453,20 @@ def _layer(lib, x, w, b, elu, stream, bf16=False):
     rc = fn(x.shape[0], x.shape[1], w.shape[0], x.data_ptr(), w.data_ptr(), b.data_ptr() if b is not None else None, y.data_ptr(), int(elu), stream)
     if rc:
         raise RuntimeError(f"{'grx_mlp_layer_bf16' if bf16 else 'grx_mlp_layer'} failed ({rc}): {tuple(x.shape)} x {tuple(w.shape)}")
+    return y
+
+
+def _hidden(lib, x, w, b, norm, stream, bf16=False):
+    """one hidden layer of the inference forward: the product with bias + ELU in its epilogue, or -- norm, an nn.LayerNorm -- the bare
+    product and grx_ln_elu_forward behind it (no mean / rstd outputs)"""
+    if norm is None:
+        return _layer(lib, x, w, b, True, stream, bf16)
+    z = _layer(lib, x, w, b, False, stream)
+    y = torch.empty_like(z)
+    rc = lib.grx_ln_elu_forward(z.shape[0], z.shape[1], z.data_ptr(), _f32c(norm.weight).data_ptr(), _f32c(norm.bias).data_ptr(), float(norm.eps),
+                                y.data_ptr(), None, None, stream)
+    if rc:
+        raise RuntimeError(f"grx_ln_elu_forward failed ({rc}): {tuple(z.shape)}")
     return y
 
 
@@ -423,14 +515,15 @@ def mlp_forward(mlp, x):
     """Inference forward of an rl.modules.MLP through libgrx_ppo.so: one MFMA launch per layer (bias + ELU in the epilogue); the
     hidden layers with bf16 operands when the MLP is set to bf16 (the output layer stays fp32)."""
     lib = load_ppo_library()
-    lin = _linears_of(mlp)
+    lin = _layers_of(mlp)
     bf16 = _bf16_hidden(mlp)
     x = _f32c(x)
     stream = torch.cuda.current_stream(x.device).cuda_stream
     with torch.cuda.device(x.device):
-        for i, (w, b) in enumerate(lin):
-            hidden = i + 1 < len(lin)
-            x = _layer(lib, x, w, b, hidden, stream, bf16 and hidden)
+        for w, b, norm in lin[:-1]:
+            x = _hidden(lib, x, w, b, norm, stream, bf16)
+        w, b, _ = lin[-1]
+        x = _layer(lib, x, w, b, False, stream)
     return x
 
 
@@ -439,14 +532,14 @@ def policy_act(mlp, std, x, eps, state_dependent=None):
     layer fused with `mu + std * eps` and Normal.log_prob summed over the actions.  state_dependent "scalar" / "log": the output
     layer is [mean | s] (2A rows) and sigma = s or exp(s) per row (grx_mlp_policy_head_sd, still one launch); `std` is not read."""
     lib = load_ppo_library()
-    lin = _linears_of(mlp)
+    lin = _layers_of(mlp)
     bf16 = _bf16_hidden(mlp)
     x = _f32c(x)
     stream = torch.cuda.current_stream(x.device).cuda_stream
     with torch.cuda.device(x.device):
-        for w, b in lin[:-1]:
-            x = _layer(lib, x, w, b, True, stream, bf16)
-        w, b = lin[-1]
+        for w, b, norm in lin[:-1]:
+            x = _hidden(lib, x, w, b, norm, stream, bf16)
+        w, b, _ = lin[-1]
         M, A = x.shape[0], w.shape[0] // (2 if state_dependent is not None else 1)
         actions, mu, sigma = (torch.empty(M, A, device=x.device, dtype=torch.float32) for _ in range(3))
         logp = torch.empty(M, device=x.device, dtype=torch.float32)

@@ -118,14 +118,89 @@ class _TrainLinearELU(torch.autograd.Function):
             torch.backends.cuda.preferred_blas_library(prev)
 
 
+def ln_elu_torch(x, weight, bias, gamma, beta, eps):
+    """the torch spelling of a LayerNorm hidden layer's forward: ELU(LayerNorm(x W^T + b)) and the product z it normalises"""
+    z = torch.addmm(bias, x, weight.t())
+    return torch.nn.functional.elu(torch.nn.functional.layer_norm(z, (z.shape[-1],), gamma, beta, eps)), z
+
+
+def ln_elu_backward_torch(dy, y, z, gamma, eps):
+    """the torch spelling of include/grx_ppo_ln.h's backward formulas: (dz, dgamma, dbeta, dbias), the three batch sums by torch's own
+    column reduction (which is why this spelling is not captured)"""
+    m = z.mean(-1, keepdim=True)
+    d = z - m
+    s = 1.0 / torch.sqrt((d * d).mean(-1, keepdim=True) + eps)
+    xh = d * s
+    g = dy * torch.where(y > 0, torch.ones_like(y), y + 1.0)
+    q = g * gamma
+    c1, c2 = q.mean(-1, keepdim=True), (q * xh).mean(-1, keepdim=True)
+    dz = s * ((q - c1) - xh * c2)
+    return dz, (g * xh).sum(0), g.sum(0), dz.sum(0)
+
+
+class _TrainLinearLNELU(torch.autograd.Function):
+    """ELU(LayerNorm(x W^T + b)) of a hidden layer of MLP(layer_norm=True) as PPO trains it.  On a HIP device: the product
+    through grx_mlp_layer without its ELU epilogue, then grx_ln_elu_forward (y, and the rows' mean and 1 / std for the backward);
+    grx_ln_elu_backward gives dz -- the gradient arriving at the product -- and the three batch sums dgamma, dbeta and the Linear's bias
+    gradient in grx_ppo_colsum's order, so no torch column reduction enters the captured step; dX and dW are _TrainLinear's products.
+    GRX_LN_FUSED=0 on a HIP device, and the function applied to CPU tensors: the torch spelling of the same formulas (ln_elu_torch,
+    ln_elu_backward_torch; not captured).  (MLP.forward itself sends CPU tensors through the plain modules under torch's autograd.)"""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, gamma, beta, eps):
+        from .fused_loss import ln_fused
+        ctx.eps, ctx.fused = float(eps), bool(x.is_cuda and ln_fused())
+        if ctx.fused:
+            from .fused_loss import _f32c, _layer, ln_elu_forward, load_ppo_library
+            with torch.cuda.device(x.device):
+                z = _layer(load_ppo_library(), _f32c(x), _f32c(weight), bias, False, torch.cuda.current_stream(x.device).cuda_stream)
+            y, mean, rstd = ln_elu_forward(z, gamma, beta, ctx.eps)
+            ctx.save_for_backward(x, weight, gamma, z, y, mean, rstd)
+            return y
+        prev = _TrainLinear._blas(x.is_cuda and weight.shape[0] == 1)
+        try:
+            y, z = ln_elu_torch(x, weight, bias, gamma, beta, ctx.eps)
+        finally:
+            torch.backends.cuda.preferred_blas_library(prev)
+        ctx.save_for_backward(x, weight, gamma, z, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        if ctx.fused:
+            from .fused_loss import ln_elu_backward
+            x, weight, gamma, z, y, mean, rstd = ctx.saved_tensors
+            dz, dgamma, dbeta, db = ln_elu_backward(dy, y, z, mean, rstd, gamma)
+        else:
+            x, weight, gamma, z, y = ctx.saved_tensors
+            dz, dgamma, dbeta, db = ln_elu_backward_torch(dy, y, z, gamma, ctx.eps)
+        prev = _TrainLinear._blas(x.is_cuda and weight.shape[0] == 1)   # (a one-column layer: _TrainLinear's hipBLASLt pin)
+        try:
+            dx = dz @ weight if ctx.needs_input_grad[0] else None   # (the first layer's input is data: no dX product)
+            return dx, dz.t() @ x, db, dgamma, dbeta, None
+        finally:
+            torch.backends.cuda.preferred_blas_library(prev)
+
+
 class MLP(nn.Module):
-    def __init__(self, input_size, output_size, hidden_dims=(256, 256, 256), activation="relu", **_):
+    def __init__(self, input_size, output_size, hidden_dims=(256, 256, 256), activation="relu", layer_norm=False, layer_norm_eps=1e-5, **_):
         super().__init__()
         self.input_size, self.output_size, self.hidden_dims = input_size, output_size, list(hidden_dims)
+        # layer_norm (DESIGN.md 4.18): every hidden layer is Linear -> LayerNorm -> ELU, the output layer stays a bare Linear
+        self.layer_norm, self.layer_norm_eps = bool(layer_norm), float(layer_norm_eps)
+        if self.layer_norm and activation != "elu":
+            raise ValueError(f"MLP: layer_norm=True needs activation='elu' (the fused LayerNorm + ELU pass), not {activation!r}")
+        if self.layer_norm and not self.layer_norm_eps > 0.0:
+            raise ValueError(f"MLP: layer_norm_eps must be above 0, not {layer_norm_eps!r}")
+        if self.layer_norm and any(not 1 <= int(h) <= 1024 for h in hidden_dims):
+            raise ValueError(f"MLP: layer_norm=True covers hidden widths of 1..1024 (include/grx_ppo_ln.h), not {list(hidden_dims)}")
         dims = [input_size] + list(hidden_dims)
         layers = []
         for a, b in zip(dims[:-1], dims[1:]):
-            layers += [nn.Linear(a, b), get_activation(activation)]
+            if self.layer_norm:
+                layers += [nn.Linear(a, b), nn.LayerNorm(b, eps=self.layer_norm_eps), get_activation(activation)]
+            else:
+                layers += [nn.Linear(a, b), get_activation(activation)]
         layers.append(nn.Linear(dims[-1], output_size))
         self.model = nn.Sequential(*layers)
         self.precision = "fp32"
@@ -156,6 +231,11 @@ class MLP(nn.Module):
         i = 0
         while i < len(mods):
             m = mods[i]
+            if isinstance(m, nn.Linear) and i + 2 < len(mods) and isinstance(mods[i + 1], nn.LayerNorm) and isinstance(mods[i + 2], nn.ELU) \
+                    and mods[i + 2].alpha == 1.0 and mods[i + 1].elementwise_affine and mods[i + 1].bias is not None:
+                x = _TrainLinearLNELU.apply(x, m.weight, m.bias, mods[i + 1].weight, mods[i + 1].bias, mods[i + 1].eps)
+                i += 3
+                continue
             if isinstance(m, nn.Linear) and i + 1 < len(mods) and isinstance(mods[i + 1], nn.ELU) and mods[i + 1].alpha == 1.0 \
                     and (_FUSED_ELU_BACKWARD or bf16):
                 x = _TrainLinearELU.apply(x, m.weight, m.bias, bf16)
@@ -201,7 +281,7 @@ class ActorCriticMLP(nn.Module):
     def __init__(self, actor_num_input, critic_num_input, actor_num_output, actor_hidden_dims=(256, 256, 256),
                  critic_hidden_dims=(256, 256, 256), activation="elu", fixed_std=False, init_noise_std=1.0,
                  set_std=True, set_noise_std=1.0, actor_output_activation=None, critic_output_activation=None, actor_output_gain=1.0,
-                 noise_std_type="scalar", state_dependent_std=False, **kwargs):
+                 noise_std_type="scalar", state_dependent_std=False, layer_norm=False, layer_norm_eps=1e-5, **kwargs):
         if kwargs:
             print("ActorCritic.__init__ got unexpected arguments, which will be ignored: " + str(list(kwargs)))
         if noise_std_type not in NOISE_STD_TYPES:
@@ -216,8 +296,12 @@ class ActorCriticMLP(nn.Module):
         self.noise_std_type, self.state_dependent_std = noise_std_type, state_dependent_std
         self.num_actor_input, self.num_actor_output = actor_num_input, actor_num_output
         self.num_critic_input, self.num_critic_output = critic_num_input, 1
-        self.actor = MLP(actor_num_input, 2 * actor_num_output if state_dependent_std else actor_num_output, actor_hidden_dims, activation)
-        self.critic = MLP(critic_num_input, 1, critic_hidden_dims, activation)
+        # layer_norm: LayerNorm between every hidden layer's product and its ELU, in actor and critic.  Off: the MLPs are
+        # built exactly as before
+        self.layer_norm = bool(layer_norm)
+        ln = {"layer_norm": True, "layer_norm_eps": layer_norm_eps} if self.layer_norm else {}
+        self.actor = MLP(actor_num_input, 2 * actor_num_output if state_dependent_std else actor_num_output, actor_hidden_dims, activation, **ln)
+        self.critic = MLP(critic_num_input, 1, critic_hidden_dims, activation, **ln)
         A = actor_num_output
         init = torch.as_tensor(init_noise_std, dtype=torch.float32) * torch.ones(A)
         last = [m for m in self.actor.model if isinstance(m, nn.Linear)][-1]

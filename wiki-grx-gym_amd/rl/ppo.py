@@ -86,6 +86,8 @@ class PPO:
         self.desired_kl, self.schedule, self.mean_kl = desired_kl, schedule, 0.0
         self.learning_rate, self.learning_rate_min, self.learning_rate_max = learning_rate, learning_rate_min, learning_rate_max
         self.actor_critic = actor_critic.to(device)
+        if precision == "bf16" and getattr(actor_critic, "layer_norm", False):   # (before set_precision's own refusal, which does not name the flag)
+            raise ValueError("PPO: --layer_norm and --precision bf16 exclude each other: the bf16 products cover Linear -> ELU hidden layers only")
         if hasattr(self.actor_critic, "set_precision"):
             self.actor_critic.set_precision(precision)
         self.storage_class = storage_class
@@ -138,6 +140,11 @@ class PPO:
             if _world() > 1:
                 raise NotImplementedError("PPO: a recurrent policy trains in one process only")
             self._use_graph = self._use_act_graph = self._two_streams = False
+        # layer normalisation in the hidden layers (rl/modules.py MLP(layer_norm=True)): Linear -> LayerNorm -> ELU, trained
+        # through _TrainLinearLNELU and captured as the default is.  Not a config key: `--layer_norm` or an assignment to train_cfg.policy sets it
+        self._layer_norm = bool(getattr(actor_critic, "layer_norm", False))
+        if self._layer_norm:
+            self._init_layer_norm(grad_penalty_coef)
         if self._device_lr:
             # rsl_rl's `Normal.set_default_validate_args = False` (actor_critic.py) is an assignment, not a call, so the
             # reference validates (and host-syncs) on every Normal(); here the validation really is off
@@ -217,6 +224,19 @@ class PPO:
         # the nine minibatch tensors (obs, cobs, actions, values, advantages, returns, old_logp, old_mu, old_sigma): how each gets its second half
         self._sym_modes = [2, 2, 2, 1, 1, 1, 1, 2, 2] if symmetry in ("augment", "both") else [2, 0, 0, 0, 0, 0, 0, 0, 0]
         self._sym_tensor_maps = [maps.obs, maps.cobs, maps.actions, None, None, None, None, maps.actions, maps.sigma]
+
+    def _init_layer_norm(self, grad_penalty_coef):
+        if self._recurrent:
+            raise ValueError("PPO: --layer_norm and --recurrent exclude each other: the recurrent policy's MLPs have no LayerNorm path")
+        if grad_penalty_coef is not None:
+            raise ValueError("PPO: --layer_norm and --grad_penalty_coef exclude each other: the penalty's second-order pass covers "
+                             "Linear -> ELU hidden layers only")
+        if _world() > 1:
+            raise NotImplementedError("PPO: --layer_norm with a world size above 1 is not implemented: it trains in one process only")
+        from .fused_loss import ln_fused
+        if self._use_graph and not ln_fused():   # the torch spelling's batch sums are torch column reductions (rl/modules.py:_TrainLinear)
+            print("PPO: GRX_LN_FUSED=0 -> the minibatch step runs eagerly (GRX_PPO_GRAPH=0)")
+            self._use_graph = self._two_streams = False
 
     def _init_value_norm(self, mode, eps):
         if self._recurrent:

@@ -127,6 +127,14 @@ class OnPolicyRunner:
         self.grad_penalty_coef = self.algorithm_cfg.get("grad_penalty_coef")
         if self.grad_penalty_coef is not None:
             self._check_grad_penalty()
+        # layer normalisation in the hidden layers: Linear -> LayerNorm -> ELU in actor and critic.  Not a config key either
+        # (`--layer_norm` or an assignment to train_cfg.policy sets it); the estimator's and RND's own networks stay without it
+        self.layer_norm = None   # the "layer_norm" entry of a checkpoint of this run: only under the flag
+        if bool(self.policy_cfg.get("layer_norm", False)):
+            self._check_layer_norm()
+            self.layer_norm = {"enabled": True, "eps": float(self.policy_cfg.get("layer_norm_eps", 1e-5))}
+        else:
+            self.policy_cfg = {k: v for k, v in self.policy_cfg.items() if k not in ("layer_norm", "layer_norm_eps")}
         self.estimator = None
         estimator_cfg = self._check_estimator(env) if bool(self.cfg.get("estimator", False)) else None
         if self.distill_from is not None:
@@ -455,6 +463,25 @@ class OnPolicyRunner:
             raise NotImplementedError("--grad_penalty_coef with a world size above 1 is not implemented: it trains in one process only")
         check_coef(self.grad_penalty_coef, who="runner")
 
+    def _check_layer_norm(self):
+        """what --layer_norm does not combine with"""
+        if self.recurrent:
+            raise ValueError("--layer_norm and --recurrent exclude each other: the recurrent policy's MLPs have no LayerNorm path")
+        if self.algorithm_cfg.get("precision", "fp32") == "bf16":
+            raise ValueError("--layer_norm and --precision bf16 exclude each other: the bf16 products cover Linear -> ELU hidden layers only")
+        if self.grad_penalty_coef is not None:
+            raise ValueError("--layer_norm and --grad_penalty_coef exclude each other: the penalty's second-order pass covers Linear -> ELU "
+                             "hidden layers only")
+        if self.distill_from is not None:
+            raise ValueError("--layer_norm and --distill_from exclude each other: a student with LayerNorm hidden layers is not implemented")
+        if bool(self.cfg.get("exact_resume", False)):
+            raise NotImplementedError("--layer_norm with --exact_resume is not implemented: a resumed run with LayerNorm hidden layers is not "
+                                      "pinned bit for bit")
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("--layer_norm with a world size above 1 is not implemented: it trains in one process only")
+        if self.policy_cfg.get("activation", "elu") != "elu":
+            raise ValueError(f"--layer_norm needs the elu activation, not {self.policy_cfg.get('activation')!r}: the fused pass is LayerNorm + ELU")
+
     def _check_value_norm(self):
         """what --value_norm does not combine with"""
         modes = ("running", "popart")   # (rl.value_norm.MODES)
@@ -656,6 +683,8 @@ class OnPolicyRunner:
             saved["estimator"] = self.estimator.checkpoint()
         if self.value_norm is not None:   # (likewise): the mode, eps and the five statistics
             saved["value_norm"] = self.algorithm.value_norm.checkpoint()
+        if self.layer_norm is not None:   # (likewise): that the hidden layers are Linear -> LayerNorm -> ELU, and the LayerNorms' eps
+            saved["layer_norm"] = dict(self.layer_norm)
         torch.save(saved, path)
         if self.exact_resume:
             torch.save(self._train_state(), train_state_path(path))
@@ -738,6 +767,10 @@ class OnPolicyRunner:
                              f"the one that was trained (pass --noise_std_type {want['std_type']}"
                              f"{' --state_dependent_std' if want['state_dependent'] else ' without --state_dependent_std'}, or set "
                              "train_cfg.policy.noise_std_type / train_cfg.policy.state_dependent_std, to match the checkpoint)")
+        if loaded.get("layer_norm") != self.layer_norm:   # (before any load_state_dict: its key error would not name the flag)
+            raise ValueError(f"{path} was saved with layer_norm={loaded.get('layer_norm')}, this runner has layer_norm={self.layer_norm}: the "
+                             f"networks would not be the ones that were trained (pass {'--layer_norm' if 'layer_norm' in loaded else 'no --layer_norm'}"
+                             ", or set train_cfg.policy.layer_norm, to match the checkpoint)")
         mine = dict(self.estimator.config) if self.estimator is not None else None
         theirs = dict(loaded["estimator"]["config"]) if "estimator" in loaded else None
         if theirs != mine:

@@ -9,6 +9,7 @@
     python -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless --estimator --estimator_targets lin_vel,base_height   (a concurrent state estimator: DESIGN.md 4.15)
     python -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless --value_norm popart                    (value normalisation, running or PopArt: DESIGN.md 4.16)
     python -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless --grad_penalty_coef 0.002              (a Lipschitz gradient penalty on the policy: DESIGN.md 4.17)
+    python -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless --layer_norm                           (Linear -> LayerNorm -> ELU hidden layers: DESIGN.md 4.18)
     torchrun --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless
 """
 import os

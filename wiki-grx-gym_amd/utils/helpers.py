@@ -123,6 +123,9 @@ def get_args(argv=None):
     p.add_argument("--state_dependent_std", action="store_true", default=False,
                    help="The actor emits its own sigma per state: its output layer is [mean | s], sigma = s (scalar) or exp(s) (log; "
                         "recommended).  Saved in the checkpoint; play needs the same flag")
+    p.add_argument("--layer_norm", action="store_true", default=False,
+                   help="Layer normalisation in the actor's and the critic's hidden layers: Linear -> LayerNorm -> ELU (needs the elu "
+                        "activation).  Saved in the checkpoint; --resume and play need the same flag")
     args = p.parse_args(argv)
     if args.obs_history < 1 or args.critic_obs_history < 1:
         raise ValueError(f"--obs_history and --critic_obs_history must be >= 1, got {args.obs_history} and {args.critic_obs_history}")
@@ -209,6 +212,8 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
             cfg_train.policy.noise_std_type = args.noise_std_type
         if getattr(args, "state_dependent_std", False):   # (likewise)
             cfg_train.policy.state_dependent_std = True
+        if getattr(args, "layer_norm", False):   # (likewise)
+            cfg_train.policy.layer_norm = True
     return env_cfg, cfg_train
 
 
