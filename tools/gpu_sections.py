@@ -53,9 +53,10 @@ for terrain in ("plane","heightfield"):
     if os.environ.get("GRX_LANES_PER_ENV") == "2" and os.environ.get("GRX_WAVES_PER_BLOCK") == "8":
         print('   lane pairs, eight waves: w0 reaches the wait for wave 5\'s rigid inertias, w0 has them:', np.median(full[:,91:93]-full[:,48:49],axis=0).astype(int).tolist())
     print('   wave 0: duration of each of the 10 sub-steps:', np.median(full[:, 64:74], axis=0).astype(int).tolist())
-    print('   obs sub-sections (cycles after tick 7): heights, noise load, side-0 puts:', np.median(full[:,11:14]-full[:,7:8],axis=0).astype(int).tolist())
+    split = bool(full[:, 154].any())   # lane quads, eight waves, GRX_TAIL_SPLIT: wave 2 stamps the end of its observations (the buffer starts zeroed)
+    if not split: print('   obs sub-sections (cycles after tick 7): heights, noise load, side-0 puts:', np.median(full[:,11:14]-full[:,7:8],axis=0).astype(int).tolist())
     print('   relative to tick 6 (FL_REW published): wave1 got FL_REW, wave1 rewards done, wave2 got FL_HZ, wave2 heights done, wave0 tick 9:', np.median(full[:,[14,15,30,31,9]]-full[:,6:7],axis=0).astype(int).tolist())
-    print('   wave 0, store section (cycles after tick 8): leg columns stored, env columns stored, tick 9 (height-block sums in):', np.median(full[:,[93,94,9]]-full[:,8:9],axis=0).astype(int).tolist())
+    if not split: print('   wave 0, store section (cycles after tick 8): leg columns stored, env columns stored, tick 9 (height-block sums in):', np.median(full[:,[93,94,9]]-full[:,8:9],axis=0).astype(int).tolist())
     if os.environ.get("GRX_QUAD_WAVES", "8") == "8":
         ev0 = full[:, 160:175] - full[:, 160:161]
         print('   timeline of sub-step 0, same events (cycles after wave 0 starts it):', {n: int(v) for n, v in zip(names_ev, np.median(ev0, axis=0)) if n != '-'})
@@ -69,14 +70,21 @@ for terrain in ("plane","heightfield"):
         print('     height scan share done          ', show(96, (1, 2, 4, 5, 6, 7)) if terrain != "plane" else '-')
         print('     reward terms done (1, 3), reset draws out (2):', show(104, (1, 2, 3)))
         print('     observation height block done   ', show(112, (4, 5, 6, 7)))
-        print('     wave 0: foot kin + timers, reward inputs out, reset done, observations done, stores done, height block picked up:',
-              np.median(full[:, [3, 6, 7, 8, 94, 9]] - t0, axis=0).astype(int).tolist())
+        if split:   # the tail split: wave 0 publishes one post-reset record; wave 2 writes the observations from it, waves 4..7 store the state columns
+            print('     wave 0: foot kin + timers, reward inputs out, reset done, post-reset record out, height block picked up:',
+                  np.median(full[:, [3, 6, 7, 8, 9]] - t0, axis=0).astype(int).tolist())
+            print('     record consumers done: observations (2), state columns (4..7):', show(152, (2, 4, 5, 6, 7)))
+        else:
+            print('     wave 0: foot kin + timers, reward inputs out, reset done, observations done, stores done, height block picked up:',
+                  np.median(full[:, [3, 6, 7, 8, 94, 9]] - t0, axis=0).astype(int).tolist())
         print('     reached the last barrier        ', rel(120))
         print('     kernel end (output rows written)', rel(128))
         idle = np.median(full[:, 120:121] - full[:, 120:128], axis=0).astype(int).tolist()
         print('     idle at the last barrier waiting for wave 0 (cycles):', idle)
         last = np.argmax(full[:, 120:128], axis=1)
         print('     wave that reaches the last barrier last, over the blocks:', np.bincount(last, minlength=8).tolist())
+        print('     last arrival at the last barrier (cycles after wave 0 reaches the barrier that ends the sub-steps): median',
+              int(np.median(full[:, 120:128].max(axis=1) - full[:, 80])), 'max', int((full[:, 120:128].max(axis=1) - full[:, 80]).max()))
     blk = full[:, 128:136].max(axis=1) - full[:, 137]
     rt0, rt1 = full[:, 136], full[:, 144:152].max(axis=1)
     print('   block time, cycles (first instruction to the last wave\'s end): median', int(np.median(blk)), 'min', int(blk.min()), 'max', int(blk.max()),

@@ -12,7 +12,12 @@
     // One LDS arena, used twice: during the sub-steps it holds the lane-compaction buffers of the rare contacts
     // (grx_rare.h: candidate list, result table, frames); after the decimation loop's barrier the same bytes are the
     // AoS staging rows of obs / pri_obs and (PIPE) the reward inputs wave 0 hands to the reward waves.
-    constexpr int OBS_BYTES = EPB * GRX_NUM_OBS * 4, PRI_BYTES = EPB * PRS * 4, RW_BYTES = PIPE ? REWIN_FLOATS * 64 * 4 : 0;
+#ifndef GRX_TAIL_SPLIT
+#define GRX_TAIL_SPLIT 1   // 0: the tail as it was -- observations and state stores on wave 0, the reward inputs as single floats (two builds of one tree compare the two)
+#endif
+    constexpr bool kTailSplit = GRX_TAIL_SPLIT && PIPE && W == 8 && LPL == 2;
+    constexpr int REWIN4 = (REWIN_FLOATS + 3) / 4;   // (kTailSplit: the reward inputs travel as quads, [REWIN4][64] float4)
+    constexpr int OBS_BYTES = EPB * GRX_NUM_OBS * 4, PRI_BYTES = EPB * PRS * 4, RW_BYTES = PIPE ? (kTailSplit ? REWIN4 * 64 * 16 : REWIN_FLOATS * 64 * 4) : 0;
     constexpr int POST_BYTES = OBS_BYTES + PRI_BYTES + RW_BYTES, PHYS_BYTES = (W == 2 || W == 8 ? 2 : 1) * RC_BYTES;
     static_assert(OBS_BYTES % 16 == 0 && PRI_BYTES % 16 == 0 && RC_BYTES % 16 == 0, "arena pieces must stay 16-byte aligned");
     constexpr int FOOTFR_BYTES = RC_FR4 * 64 * 16, ANCH_BYTES = 16 * 64 * 4;   // (s_anch: anchors x 4, y 4, mask 1, approach speeds 4, foot |w| sums 3)
@@ -52,6 +57,14 @@
     __shared__ float4 s_fx[W == 8 && LPL == 2 ? 8 * 64 : 1];           // W == 8: base-level 6 x 6 (wave 0 -> wave 5) and its factorisation (wave 5 -> wave 0)
     __shared__ int s_flag[FL_COUNT];
     const PipeLds L = {s_bq, s_q, s_wc, s_pb, reinterpret_cast<float4*>(s_wr), s_flag, s_xk, s_sb, s_fx};
+    // Lane quads, eight waves: behind reset_idx wave 0 writes ONE record of final values -- TAIL_LEG4 quads per lane for its leg, TAIL_ENV4 for its env
+    // (grx_wavepipe.h) -- and raises FL_HZ to 2, then 3; wave 2 turns it into the observation rows, waves 4..7 store the state columns from it, each lane the slot
+    // it would have held on wave 0.  The record is a third use of the arena: behind the staging rows and the reward inputs, in front of s_anch, where only
+    // the sub-steps keep anything (compaction buffers, foot frames) -- the barrier that ends them orders the reuse, and the DBG twins have the bytes too.
+    constexpr int REC_OFF = (POST_BYTES + 15) / 16 * 16;
+    static_assert(!kTailSplit || REC_OFF + (TAIL_LEG4 + TAIL_ENV4) * 64 * 16 <= PHYS_BYTES + FOOTFR_BYTES, "the post-reset record must fit between the reward inputs and s_anch");
+    float4* const s_rec = reinterpret_cast<float4*>(s_arena + (kTailSplit ? REC_OFF : 0));   // [TAIL_LEG4][64]
+    float4* const s_renv = s_rec + TAIL_LEG4 * 64;                                           // [TAIL_ENV4][64]
     const int tid = threadIdx.x;
 #ifdef GRX_PROFILE_SECTIONS   // the block's first instruction, as wall time (100 MHz: comparable across blocks) and as cycles
     if (tid == 0) { P.prof[(size_t)blockIdx.x * GRX_PROF_SLOTS + 136] = (long long)__builtin_amdgcn_s_memrealtime(); P.prof[(size_t)blockIdx.x * GRX_PROF_SLOTS + 137] = clock64(); }
@@ -218,6 +231,13 @@
                 flag_wait(s_flag + FL_REW, 1);
                 RewIn rin;
                 int i = 0;
+                if (kTailSplit) {
+                    float w_[4 * REWIN4];
+                    const float4* z = reinterpret_cast<const float4*>(s_rw) + lane;
+#pragma unroll
+                    for (int r = 0; r < REWIN4; ++r) { const float4 t = z[r * 64]; w_[4 * r] = t.x; w_[4 * r + 1] = t.y; w_[4 * r + 2] = t.z; w_[4 * r + 3] = t.w; }
+                    rewin_fields(rin, [&](float& x) { x = w_[i++]; });
+                } else
                 rewin_fields(rin, [&](float& x) { x = s_rw[(i++) * 64 + lane]; });
                 if (W == 8 && HF) rin.feet_height = scan_feet_height(P, s_flag, s_hsum, rin.feet_height, nh, lane);
                 reward_and_sums<2>(P, C, rin, lane, side, e, N, act, s_stat, es_w3, s_rwp, s_flag + FL_RWB, nullptr,
@@ -229,6 +249,13 @@
                 GRX_TICKW(14);
                 RewIn rin;
                 int i = 0;
+                if (kTailSplit) {
+                    float w_[4 * REWIN4];
+                    const float4* z = reinterpret_cast<const float4*>(s_rw) + lane;
+#pragma unroll
+                    for (int r = 0; r < REWIN4; ++r) { const float4 t = z[r * 64]; w_[4 * r] = t.x; w_[4 * r + 1] = t.y; w_[4 * r + 2] = t.z; w_[4 * r + 3] = t.w; }
+                    rewin_fields(rin, [&](float& x) { x = w_[i++]; });
+                } else
                 rewin_fields(rin, [&](float& x) { x = s_rw[(i++) * 64 + lane]; });
                 if (W == 8 && HF) rin.feet_height = scan_feet_height(P, s_flag, s_hsum, rin.feet_height, nh, lane);
                 float a_ll1[LEG];   // DBG: the injected last_last_actions (action_diff_diff is one of this wave's terms)
@@ -264,6 +291,135 @@
                 s_hsum[wv * 64 + lane] = env_sum(part);
                 flag_set(s_flag + FL_BHO1 + (wv - 1), 1, lane);
                 if (wv == 2) GRX_TICKW(31);
+            }
+            if (kTailSplit && wv == 2) {
+                // ---- compute_observations (legged_robot.py:442-452, legged_robot_fftai.py:148-167, gr1t1.py:281-336) from wave 0's post-reset record:
+                // the expressions, the noise words (s_nz, this lane's slot) and their order are those of the code on wave 0 below
+                U4 nzb[NZB];   // (wave 1 left them during the sub-steps: read while the record is still on its way)
+                if (P.add_noise && !noise_in) {
+                    const uint32_t* z = s_nz + lane;
+#pragma unroll
+                    for (int b = 0; b < NZB; ++b) { nzb[b].x = z[(b * 4 + 0) * 64]; nzb[b].y = z[(b * 4 + 1) * 64]; nzb[b].z = z[(b * 4 + 2) * 64]; nzb[b].w = z[(b * 4 + 3) * 64]; }
+                }
+                flag_wait(s_flag + FL_HZ, 2);
+                const float4* r_ = s_rec + lane;
+                const float4 r0 = r_[0 * 64], r1 = r_[1 * 64], r2 = r_[2 * 64], r3 = r_[3 * 64], r8 = r_[8 * 64], r11 = r_[11 * 64];
+                const float oq[LEG] = {r0.x, r0.y, r0.z, r0.w, r1.x}, oqd[LEG] = {r1.y, r1.z, r1.w, r2.x, r2.y}, oa[LEG] = {r2.z, r2.w, r3.x, r3.y, r3.z};
+                float* prow = s_pri + el * PRS;
+                float* orow = s_obs + el * GRX_NUM_OBS;
+                const float clipo = P.clip_observations;
+                // item: index within the lane's stream (compile-time); slot0: first block slot of that stream
+                auto put = [&](int idx, float val, float nscale, int item, int slot0) {
+                    float pv = fminf(fmaxf(val, -clipo), clipo);
+                    prow[idx] = pv;  // pri_obs copies obs BEFORE noise (SURVEY Q6)
+                    float ov = val;
+                    if (P.add_noise && nscale != 0.f) {
+                        float u;
+                        if (noise_in) u = noise_in[(size_t)e * GRX_NUM_OBS + idx];
+                        else {
+                            const U4 o = nzb[slot0 + (item >> 2)];
+                            const int wsel = item & 3;
+                            u = grx_u01(wsel == 0 ? o.x : (wsel == 1 ? o.y : (wsel == 2 ? o.z : o.w)));
+                        }
+                        ov += (2.f * u - 1.f) * nscale;
+                    }
+                    orow[idx] = fminf(fmaxf(ov, -clipo), clipo);
+                };
+                if (side == 0) {
+                    const float4* v_ = s_renv + lane;
+                    const float4 v3_ = v_[3 * 64], v4 = v_[4 * 64], v5 = v_[5 * 64], v6 = v_[6 * 64];
+                    const V3 blv = v3(v4.x, v4.y, v4.z), bav = v3(v4.w, v5.x, v5.y), pg = v3(v5.z, v5.w, v6.x);
+                    put(0, v3_.y, 0.f, 0, 4); put(1, v3_.z, 0.f, 0, 4); put(2, v3_.w, 0.f, 0, 4);
+                    const float na = P.noise_ang_vel * P.noise_level * P.obs_scale_ang_vel;
+                    put(3, bav.x * P.obs_scale_ang_vel, na, 0, 4); put(4, bav.y * P.obs_scale_ang_vel, na, 1, 4); put(5, bav.z * P.obs_scale_ang_vel, na, 2, 4);
+                    const float ng = P.noise_gravity * P.noise_level * P.obs_scale_gravity;
+                    put(6, pg.x * P.obs_scale_gravity, ng, 3, 4); put(7, pg.y * P.obs_scale_gravity, ng, 4, 4); put(8, pg.z * P.obs_scale_gravity, ng, 5, 4);
+                    prow[GRX_NUM_OBS + 0] = fminf(fmaxf(blv.x * P.obs_scale_lin_vel, -clipo), clipo);
+                    prow[GRX_NUM_OBS + 1] = fminf(fmaxf(blv.y * P.obs_scale_lin_vel, -clipo), clipo);
+                    prow[GRX_NUM_OBS + 2] = fminf(fmaxf(blv.z * P.obs_scale_lin_vel, -clipo), clipo);
+                }
+                const float np_ = P.noise_dof_pos * P.noise_level * P.obs_scale_dof_pos;
+                const float nv = P.noise_dof_vel * P.noise_level * P.obs_scale_dof_vel;
+                const float nac = P.noise_action * P.noise_level * P.obs_scale_action;
+#pragma unroll
+                for (int k = 0; k < LEG; ++k) {
+                    put(9 + j0 + k, (oq[k] - C.body[k].q0) * P.obs_scale_dof_pos, np_, k, 0);
+                    put(9 + GRX_ND + j0 + k, oqd[k] * P.obs_scale_dof_vel, nv, 5 + k, 0);
+                    put(9 + 2 * GRX_ND + j0 + k, oa[k] * P.obs_scale_action, nac, 10 + k, 0);
+                }
+                float feet_height = r11.y;   // (the heightfield with a scan: the foot's z so far, as on the reward waves)
+                if (HF && P.measure_heights) feet_height = scan_feet_height(P, s_flag, s_hsum, feet_height, nh, lane);
+                prow[GRX_NUM_OBS + 4 + side] = r8.z;
+                prow[GRX_NUM_OBS + 6 + side] = fminf(fmaxf(feet_height * P.obs_scale_height, -clipo), clipo);
+                if (act0) GCOL(P.feet_height, (size_t)side * N + e) = feet_height;
+                GRX_TICKV(152);
+            } else if (kTailSplit && wv >= 4) {
+                // ---- store state (SoA) -- history: last_actions = actions, last_dof_vel = dof_vel (legged_robot.py:299-300): a quarter of the columns each, the
+                // env's on the wave that shares wave 0's SIMD (idle by now), the lightest quarter on the one that shares the second reward wave's
+                flag_wait(s_flag + FL_HZ, 3);
+                const float4* r_ = s_rec + lane;
+                if (wv == 4) {
+                    if (act0 && side == 0) {
+                        const float4* v_ = s_renv + lane;
+                        const float4 v0 = v_[0 * 64], v1 = v_[1 * 64], v2 = v_[2 * 64], v3_ = v_[3 * 64], v4 = v_[4 * 64], v5 = v_[5 * 64], v6 = v_[6 * 64], v7 = v_[7 * 64], v8 = v_[8 * 64];
+                        const float rs[13] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, v2.x, v2.y, v2.z, v2.w, v3_.x};
+#pragma unroll
+                        for (int i = 0; i < 13; ++i) GCOL(P.root, (size_t)i * N + e) = rs[i];
+                        GCOL(P.commands, e) = v3_.y; GCOL(P.commands, (size_t)N + e) = v3_.z; GCOL(P.commands, 2 * (size_t)N + e) = v3_.w;
+                        GCOL(P.base_lin_vel, e) = v4.x; GCOL(P.base_lin_vel, (size_t)N + e) = v4.y; GCOL(P.base_lin_vel, 2 * (size_t)N + e) = v4.z;
+                        GCOL(P.base_ang_vel, e) = v4.w; GCOL(P.base_ang_vel, (size_t)N + e) = v5.x; GCOL(P.base_ang_vel, 2 * (size_t)N + e) = v5.y;
+                        GCOL(P.proj_grav, e) = v5.z; GCOL(P.proj_grav, (size_t)N + e) = v5.w; GCOL(P.proj_grav, 2 * (size_t)N + e) = v6.x;
+                        GCOL(P.origins, e) = v6.y; GCOL(P.origins, (size_t)N + e) = v6.z; GCOL(P.origins, 2 * (size_t)N + e) = v6.w;
+                        GCOL(P.levels, e) = __float_as_int(v7.x);
+                        GCOL(P.ep_len, e) = (long long)(((unsigned long long)__float_as_uint(v7.z) << 32) | (unsigned long long)__float_as_uint(v7.y));
+                        GCOL(P.reset, e) = __float_as_int(v7.w);
+                        GCOL(P.time_out, e) = __float_as_int(v8.x);
+                        GCOL(P.term_contact, e) = __float_as_int(v8.y);
+                    }
+                } else if (wv == 5) {
+                    const float4 r0 = r_[0 * 64], r1 = r_[1 * 64], r2 = r_[2 * 64], r8 = r_[8 * 64];
+                    const float oq[LEG] = {r0.x, r0.y, r0.z, r0.w, r1.x}, oqd[LEG] = {r1.y, r1.z, r1.w, r2.x, r2.y};
+                    if (act0) {
+#pragma unroll
+                        for (int k = 0; k < LEG; ++k) {
+                            const size_t o = (size_t)(j0 + k) * N + e;
+                            GCOL(P.q, o) = oq[k]; GCOL(P.qd, o) = oqd[k]; GCOL(P.last_dof_vel, o) = oqd[k];
+                        }
+                        GCOL(P.air_time, (size_t)side * N + e) = r8.x;
+                        GCOL(P.land_time, (size_t)side * N + e) = r8.y;
+                        GCOL(P.feet_contact, (size_t)side * N + e) = r8.z != 0.f ? 1 : 0;
+                        GCOL(P.avg_force, (size_t)side * N + e) = r8.w;
+                    }
+                } else if (wv == 6) {
+                    const float4 r5 = r_[5 * 64], r6 = r_[6 * 64], r7 = r_[7 * 64], r9 = r_[9 * 64], r10 = r_[10 * 64], r11 = r_[11 * 64];
+                    const float ax[4] = {r5.x, r5.y, r5.z, r5.w}, ay[4] = {r6.x, r6.y, r6.z, r6.w}, av[4] = {r7.x, r7.y, r7.z, r7.w};
+                    const float ff[3] = {r9.x, r9.y, r9.z}, fp[3] = {r9.w, r10.x, r10.y}, as_[3] = {r10.z, r10.w, r11.x};
+                    if (act0) {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            GCOL(P.anchors, (size_t)((side * 4 + i) * 3 + 0) * N + e) = ax[i];
+                            GCOL(P.anchors, (size_t)((side * 4 + i) * 3 + 1) * N + e) = ay[i];
+                            GCOL(P.anchors, (size_t)((side * 4 + i) * 3 + 2) * N + e) = av[i];
+                        }
+#pragma unroll
+                        for (int i = 0; i < 3; ++i) {
+                            GCOL(P.feet_force, (size_t)(side * 3 + i) * N + e) = ff[i];
+                            GCOL(P.feet_pos, (size_t)(side * 3 + i) * N + e) = fp[i];
+                            GCOL(P.avg_speed, (size_t)(side * 3 + i) * N + e) = as_[i];
+                        }
+                    }
+                } else {
+                    const float4 r2 = r_[2 * 64], r3 = r_[3 * 64], r4 = r_[4 * 64];
+                    const float oa[LEG] = {r2.z, r2.w, r3.x, r3.y, r3.z}, ot[LEG] = {r3.w, r4.x, r4.y, r4.z, r4.w};
+                    if (act0) {
+#pragma unroll
+                        for (int k = 0; k < LEG; ++k) {
+                            const size_t o = (size_t)(j0 + k) * N + e;
+                            GCOL(P.last_actions, o) = oa[k]; GCOL(P.actions, o) = oa[k]; GCOL(P.torques, o) = ot[k];
+                        }
+                    }
+                }
+                GRX_TICKV(152);
             }
             if (P.publish_rbs && (W == 8 || wv < 4)) {   // every URDF link frame of the state wave 0 published after the last sub-step: a third (eight waves: a seventh) on each helper wave
                 float b_[13]; pipe_base_load(s_bq, el, b_);
@@ -593,6 +749,13 @@
         rin.reset = reset ? 1.f : 0.f; rin.time_out = time_out ? 1.f : 0.f;
         if (PIPE) {
             int i = 0;
+            if (kTailSplit) {
+                float w_[4 * REWIN4] = {};
+                rewin_fields(rin, [&](float& x) { w_[i++] = x; });
+                float4* z = reinterpret_cast<float4*>(s_rw) + lane;
+#pragma unroll
+                for (int r = 0; r < REWIN4; ++r) z[r * 64] = f4(w_[4 * r], w_[4 * r + 1], w_[4 * r + 2], w_[4 * r + 3]);
+            } else
             rewin_fields(rin, [&](float& x) { s_rw[(i++) * 64 + lane] = x; });
             flag_set(s_flag + FL_REW, 1, lane);
         } else if constexpr (kBaseTerms) {   // (grx_step_kernel_base*: legged_gym's base terms join the total before the clip)
@@ -653,8 +816,41 @@
         bho = nh > 0 ? sum / (float)nh : 0.f;
     }
     GRX_TICK(11);
-    float* orow = s_obs + el * GRX_NUM_OBS;
     const float clipo = P.clip_observations;
+    if (kTailSplit) {   // the post-reset record (layout: grx_wavepipe.h); observations and stores follow on waves 2 and 4..7
+        // first what the observations read (wave 2 ends last of the helpers): FL_HZ = 2; then the rest for the stores: FL_HZ = 3
+        float4* r_ = s_rec + lane;
+        float4* v_ = s_renv + lane;
+        r_[0 * 64] = f4(st.q[0], st.q[1], st.q[2], st.q[3]);
+        r_[1 * 64] = f4(st.q[4], st.qd[0], st.qd[1], st.qd[2]);
+        r_[2 * 64] = f4(st.qd[3], st.qd[4], a_cur[0], a_cur[1]);
+        r_[3 * 64] = f4(a_cur[2], a_cur[3], a_cur[4], torque[0]);
+        r_[8 * 64] = f4(air_time * (contact_filt ? 0.f : 1.f), land_time, feet_contact_obs ? 1.f : 0.f, avg_force);   // legged_robot_fftai.py:97
+        r_[11 * 64] = f4(avg_speed.z, feet_height, 0.f, 0.f);
+        v_[3 * 64] = f4(st.ang.z, ea.cmd[0], ea.cmd[1], ea.cmd[2]);
+        v_[4 * 64] = f4(blv.x, blv.y, blv.z, bav.x);
+        v_[5 * 64] = f4(bav.y, bav.z, pg.x, pg.y);
+        v_[6 * 64] = f4(pg.z, ea.origin[0], ea.origin[1], ea.origin[2]);
+        flag_set(s_flag + FL_HZ, 2, lane);
+        r_[4 * 64] = f4(torque[1], torque[2], torque[3], torque[4]);
+        r_[5 * 64] = f4(st.ax[0], st.ax[1], st.ax[2], st.ax[3]);
+        r_[6 * 64] = f4(st.ay[0], st.ay[1], st.ay[2], st.ay[3]);
+        float av[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) av[i] = (st.anchor_on >> i) & 1u ? fmaxf(st.vimp[i], 1e-6f) : 0.f;
+        r_[7 * 64] = f4(av[0], av[1], av[2], av[3]);
+        r_[9 * 64] = f4(so.foot_force.x, so.foot_force.y, so.foot_force.z, fk.pos.x);
+        r_[10 * 64] = f4(fk.pos.y, fk.pos.z, avg_speed.x, avg_speed.y);
+        v_[0 * 64] = f4(st.pos.x, st.pos.y, st.pos.z, st.qx);
+        v_[1 * 64] = f4(st.qy, st.qz, st.qw, st.vel.x);
+        v_[2 * 64] = f4(st.vel.y, st.vel.z, st.ang.x, st.ang.y);
+        v_[7 * 64] = f4(__int_as_float(ea.level), __int_as_float((int)(uint32_t)(unsigned long long)ep_len), __int_as_float((int)(uint32_t)((unsigned long long)ep_len >> 32)),
+                        __int_as_float(reset ? 1 : 0));
+        v_[8 * 64] = f4(__int_as_float(time_out ? 1 : 0), __int_as_float(term_contact ? 1 : 0), 0.f, 0.f);
+        flag_set(s_flag + FL_HZ, 3, lane);
+        GRX_TICK(8);
+    } else {
+    float* orow = s_obs + el * GRX_NUM_OBS;
     // observation noise (noise_blocks): with 4 waves per block wave 1 computed the blocks while wave 0 loaded state
     U4 nzb[NZB];
     if (P.add_noise && !noise_in) {
@@ -757,6 +953,7 @@
         GCOL(P.time_out, e) = time_out ? 1 : 0;
         GCOL(P.term_contact, e) = term_contact ? 1 : 0;
     }
+    }   // !kTailSplit
     GRX_TICK(94);
     if (PIPE) {   // base_heights_offset: the helper waves' partial sums of the observation height block
         if (W == 8) {

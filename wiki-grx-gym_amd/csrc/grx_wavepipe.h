@@ -93,6 +93,13 @@ constexpr int PB4 = 2;    // quads per chain body from wave 2: rigid-body bias f
 constexpr int WC4 = 15;   // contact wrenches about O: thigh quads 0-1, shank 2-3, foot 4-6 (wrench 6 + foot link velocity 3);
                           // quads 7-14: self-collision (grx_self.h) on thigh, shank, foot, base lump + the forces on base-lump links
 constexpr int Q4 = 3;     // q 5, qd 5 of the lane's leg
+// The post-reset record of the lane-quad eight-wave tail (wave 0 -> wave 2: observations, -> waves 4..7: state columns), FINAL values only:
+//   leg quads  0-4: q 5, qd 5, clipped actions 5, torques 5;  5-7: friction anchors x 4, y 4, stored approach speeds 4;
+//              8: air_time (as stored), land_time, feet_contact (0 / 1), avg_force;  9-11: foot force 3, foot position 3, avg_speed 3, feet_height
+//              before the height scan's mean (the consumer finishes it: scan_feet_height)
+//   env quads  0-3: root state 13, commands 3;  4-6: base_lin_vel 3, base_ang_vel 3, projected gravity 3, origin 3;
+//              7: level, ep_len (two words), reset;  8: time_out, termination contact (integers as bit patterns)
+constexpr int TAIL_LEG4 = 12, TAIL_ENV4 = 9;
 
 struct PipeLds {
     float4* bq;    // [4][EPB]    base state at the start of the sub-step: (pos, q.x) (q.yzw, vel.x) (vel.yz, ang.xy) (ang.z, -, -, -)
