@@ -2,7 +2,8 @@
 quad, tree, tree16, generic, their *_trimesh heads and one *_base entry per family.  With one sub-step per step nothing amplifies
 rounding, so a row is either inside SUBSTEP_BAND -- SENS_K x what the fp32 oracle shows against the fp64 one on the same trajectory -- or
 counted against the scene's caps (substep.scene_caps): no twins, no outlier fractions, no hard-cap table.  A contact impulse, friction
-anchor, face contact or self-collision force that is off by a newton fails here.
+anchor, face contact or self-collision force that is off by a newton fails here.  The *_far cases hold the same kernels at the coordinates of
+a real run's far side (189 m on the plane grid, raster cell ~1850 of the curriculum grid) to the fp32 oracle's own error there.
 
 The oracle side of a scene is computed once and shared by the layouts next to it.  The observed maxima per (scene, layout, tensor) and their
 ratio to the fp32 oracle's are printed, and appended to the jsonl file GRX_SUBSTEP_LOG names, if set (profiles/substep_hip.jsonl holds an
@@ -26,7 +27,12 @@ CASES = ([("plane", l) for l in FUSED] + [("plane_t2", l) for l in (8, "quad")]
          + [("legs", l) for l in (1, 8, "quad4", "quad")]
          + [(s, l) for s in ("slope_hf", "slope_tm", "stairs_hf", "stairs_tm") for l in (1, 8, "quad")]
          + [(s, l) for s in ("full_plane", "full_stairs") for l in TREES]
-         + [("base_plane", "base")] + [("base_full_plane", l) for l in TREES])  # one *_base entry per family
+         + [("base_plane", "base")] + [("base_full_plane", l) for l in TREES]   # one *_base entry per family
+         # 128-256 m from the origin, where pos, the anchors and terrain_locate's cell index carry 8-32 x the rounding: the last 64 envs of a 4096-env
+         # plane grid, and the far tile of the 10 x 20 curriculum raster (bands and caps of their own: substep.SUBSTEP_BAND, scene_caps)
+         + [("plane_far", l) for l in FUSED] + [("plane_t2_far", l) for l in (8, "quad")] + [("base_plane_far", "base")]
+         + [(s, l) for s in ("slope_hf_far", "slope_tm_far") for l in (1, 8, "quad")]
+         + [(s, l) for s in ("full_plane_far", "full_slope_tm_far") for l in TREES])
 
 
 def select(monkeypatch, scene, layout):
