@@ -292,4 +292,7 @@ int grx_rnd_reward(int N, int E, const float* pred, const float* targ, float gam
 /* ... and layer normalisation in the hidden layers: LayerNorm + ELU behind a layer's product, forward and backward,
  * csrc/grx_ppo_ln.hip in the same library */
 #include "grx_ppo_ln.h"
+/* ... and multi-critic PPO: a value head, a GAE pass and a value loss per group of reward terms,
+ * csrc/grx_ppo_mc.hip in the same library */
+#include "grx_ppo_mc.h"
 #endif

@@ -281,7 +281,8 @@ class ActorCriticMLP(nn.Module):
     def __init__(self, actor_num_input, critic_num_input, actor_num_output, actor_hidden_dims=(256, 256, 256),
                  critic_hidden_dims=(256, 256, 256), activation="elu", fixed_std=False, init_noise_std=1.0,
                  set_std=True, set_noise_std=1.0, actor_output_activation=None, critic_output_activation=None, actor_output_gain=1.0,
-                 noise_std_type="scalar", state_dependent_std=False, layer_norm=False, layer_norm_eps=1e-5, **kwargs):
+                 noise_std_type="scalar", state_dependent_std=False, layer_norm=False, layer_norm_eps=1e-5, num_critic_outputs=1,
+                 **kwargs):
         if kwargs:
             print("ActorCritic.__init__ got unexpected arguments, which will be ignored: " + str(list(kwargs)))
         if noise_std_type not in NOISE_STD_TYPES:
@@ -295,13 +296,16 @@ class ActorCriticMLP(nn.Module):
         super().__init__()
         self.noise_std_type, self.state_dependent_std = noise_std_type, state_dependent_std
         self.num_actor_input, self.num_actor_output = actor_num_input, actor_num_output
-        self.num_critic_input, self.num_critic_output = critic_num_input, 1
+        # num_critic_outputs: one value head per reward group of --reward_groups; 1 builds the critic exactly as before
+        if int(num_critic_outputs) != num_critic_outputs or not 1 <= int(num_critic_outputs) <= 8:
+            raise ValueError(f"num_critic_outputs must be an integer in 1..8, not {num_critic_outputs!r}")
+        self.num_critic_input, self.num_critic_output = critic_num_input, int(num_critic_outputs)
         # layer_norm: LayerNorm between every hidden layer's product and its ELU, in actor and critic.  Off: the MLPs are
         # built exactly as before
         self.layer_norm = bool(layer_norm)
         ln = {"layer_norm": True, "layer_norm_eps": layer_norm_eps} if self.layer_norm else {}
         self.actor = MLP(actor_num_input, 2 * actor_num_output if state_dependent_std else actor_num_output, actor_hidden_dims, activation, **ln)
-        self.critic = MLP(critic_num_input, 1, critic_hidden_dims, activation, **ln)
+        self.critic = MLP(critic_num_input, self.num_critic_output, critic_hidden_dims, activation, **ln)
         A = actor_num_output
         init = torch.as_tensor(init_noise_std, dtype=torch.float32) * torch.ones(A)
         last = [m for m in self.actor.model if isinstance(m, nn.Linear)][-1]

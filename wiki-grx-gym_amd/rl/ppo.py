@@ -69,7 +69,7 @@ class PPO:
                  weight_decay=0.0, max_grad_norm=1.0, use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01,
                  device="cpu", storage_class="RolloutStorage", precision="fp32", symmetry=None, symmetry_coef=1.0, symmetry_maps=None,
                  smooth=None, smooth_temporal_coef=0.1, smooth_spatial_coef=0.1, smooth_sigma=0.05, value_norm=None, value_norm_eps=1e-5,
-                 grad_penalty_coef=None, **kwargs):
+                 grad_penalty_coef=None, reward_groups=None, reward_group_weights=None, **kwargs):
         if kwargs:
             print("PPO.__init__ got unexpected arguments, which will be ignored: " + str(list(kwargs)))
         # precision="bf16": every hidden layer of actor and critic multiplies bf16 operands into fp32 accumulators -- in the rollout's
@@ -184,6 +184,12 @@ class PPO:
         self.grad_penalty_coef, self.mean_grad_penalty = None, 0.0
         if grad_penalty_coef is not None:
             self._init_grad_penalty(grad_penalty_coef)
+        # multi-critic PPO (rl/multi_critic.py): the critic has a value head per group of reward terms, GAE and the advantage
+        # normalisation run per group, the value loss is the sum over the heads.  Not a config key: `--reward_groups` or an assignment to
+        # train_cfg.algorithm sets it (the runner parses the spec against the env's active terms); None imports nothing of it
+        self.multi_critic = None
+        if reward_groups is not None:
+            self._init_multi_critic(reward_groups, reward_group_weights)
         self.num_updates = 0
         self._params = [p for p in self.actor_critic.parameters() if p.requires_grad]
         n = sum(p.numel() for p in self._params)
@@ -269,6 +275,39 @@ class PPO:
         self.grad_penalty_coef = coef
         self._gp_sum = torch.zeros(1, device=self.device)   # the update's sum of P (finite steps), read back once per update
 
+    def _init_multi_critic(self, groups, weights):
+        why = "the per-group critic, GAE and value loss cover the plain fp32 MLP policy on the plain minibatch"
+        if self._recurrent:
+            raise ValueError(f"PPO: --reward_groups and --recurrent exclude each other: {why}")
+        if self.value_norm is not None:
+            raise ValueError("PPO: --reward_groups and --value_norm exclude each other: return statistics per value head are not implemented")
+        if self.symmetry is not None:
+            raise ValueError(f"PPO: --reward_groups and --symmetry exclude each other: {why}")
+        if self.smooth is not None:
+            raise ValueError(f"PPO: --reward_groups and --smooth exclude each other: {why}")
+        if self.grad_penalty_coef is not None:
+            raise ValueError(f"PPO: --reward_groups and --grad_penalty_coef exclude each other: {why}")
+        if self._state_dependent:
+            raise ValueError("PPO: --reward_groups and --state_dependent_std exclude each other: the multi-critic loss takes one sigma per "
+                             "action")
+        if self._layer_norm:
+            raise ValueError(f"PPO: --reward_groups and --layer_norm exclude each other: {why}")
+        if self.precision == "bf16":
+            raise ValueError(f"PPO: --reward_groups and --precision bf16 exclude each other: {why}")
+        if _world() > 1:
+            raise NotImplementedError("PPO: --reward_groups with a world size above 1 is not implemented: the advantage statistics are per "
+                                      "process")
+        from .multi_critic import MultiCritic, fused_enabled
+        mc = MultiCritic(groups, weights, self.device)
+        heads = getattr(self.actor_critic, "num_critic_output", 1)
+        if heads != mc.K:
+            raise ValueError(f"PPO: --reward_groups names {mc.K} groups, the critic has {heads} outputs (ActorCriticMLP(num_critic_outputs="
+                             f"{mc.K}))")
+        self.multi_critic = mc
+        if self._use_graph and not fused_enabled():   # (the torch spelling's per-head means are not what the captured step is pinned on)
+            print("PPO: GRX_MC_FUSED=0 -> the minibatch step runs eagerly (GRX_PPO_GRAPH=0)")
+            self._use_graph = self._two_streams = False
+
     def _init_smooth(self, smooth, coef_t, coef_s, sigma):
         from .smooth import blocks, check_values
         succ, pert = blocks(smooth)
@@ -300,6 +339,8 @@ class PPO:
             return
         self.storage = RolloutStorage(num_envs, num_transitions_per_env, [ac.num_actor_input], [ac.num_critic_input],
                                       [ac.num_actor_output], self.device)
+        if self.multi_critic is not None:   # (the K-wide values / rewards / returns beside it)
+            self.multi_critic.init_storage(num_envs, num_transitions_per_env)
 
     def test_mode(self):
         self.actor_critic.eval()
@@ -432,6 +473,8 @@ class PPO:
         t = self.transition
         st = self.storage
         self._join_critic()
+        if self.multi_critic is not None:   # the heads' values and the group rewards into their own rows; the scalar store gets sum_k v_k
+            t.values = self.multi_critic.store(st.step, t.values, infos.get("time_outs"), self.gamma)
         if self._fused_store and rewards.is_cuda and t.observations is not None and t.observations.is_contiguous():
             if st.step >= st.num_transitions_per_env:
                 raise AssertionError("Rollout buffer overflow")
@@ -460,6 +503,8 @@ class PPO:
     def rnd_step(self, frame, step):
         """after process_env_step of rollout step `step`: the intrinsic reward of the raw frame the env just returned, added to the
         storage's reward row of that step in place (the row holds the env's reward and the time-out bootstrap by then)"""
+        if self.multi_critic is not None:   # (the runner refuses the pair before it builds anything; a caller that assigns `rnd` itself ends here)
+            raise ValueError("PPO: --reward_groups and --rnd exclude each other: the intrinsic reward belongs to no group")
         self.rnd.rollout_step(frame, self.storage.rewards[step], step)
 
     def compute_returns(self, last_critic_obs):
@@ -472,6 +517,9 @@ class PPO:
         if self.value_norm is not None:   # GAE in reward units, the statistics' update, then the storage's values / returns normalised in place
             self.value_norm.compute_returns(self.storage, self.value_norm.denormalize(last_values), self.gamma, self.lam,
                                             critic=self.actor_critic.critic)
+            return
+        if self.multi_critic is not None:   # GAE and the advantage normalisation per group, the advantages their weighted sum
+            self.multi_critic.compute_returns(self.storage, last_values, self.gamma, self.lam)
             return
         self.storage.compute_returns(last_values, self.gamma, self.lam)
 
@@ -520,6 +568,8 @@ class PPO:
             return self._update_smooth()
         if self.grad_penalty_coef is not None:
             return self._update_gp()
+        if self.multi_critic is not None:
+            return self._update_mc()
         if self._device_lr:
             # For these GEMM shapes (batch ~10^4 rows, 39..512 columns, fp32) rocBLAS's kernel choices beat hipBLASLt's by 2x
             # on the weight-gradient products dY^T X (27-48 us against 66-73 us, tools/gpu_gemm_probe.py).  torch's BLAS
@@ -681,6 +731,10 @@ class PPO:
         (symmetry "loss": the mirrored rows behind them have no PPO loss)"""
         ac = self.actor_critic
         adaptive = self.desired_kl is not None and self.schedule == "adaptive"
+        if self.multi_critic is not None:   # (value / returns / target_values are [mb, K]: the value loss is the sum over the heads)
+            return self.multi_critic.loss(mu, _noise_std(ac), value, actions, old_logp, old_mu, old_sigma, advantages, returns, target_values,
+                                          self.clip_param, self.value_loss_coef, self.entropy_coef, self.use_clipped_value_loss, adaptive,
+                                          self._loss_is_fused())
         if self._state_dependent and self._loss_is_fused():   # (mu is the raw [mean | s]: the gradient lands on it in one launch)
             out = fused_ppo_loss_sd(mu, value, actions, old_logp, old_mu, old_sigma, advantages, returns, target_values,
                                     ac.noise_std_type == "log", self.clip_param, self.value_loss_coef, self.entropy_coef,
@@ -974,14 +1028,53 @@ class PPO:
         self.num_updates = self.num_learning_epochs * self.num_mini_batches
         return mean_value_loss / self.num_updates, mean_surrogate_loss / self.num_updates
 
+    # ------------------------------------------------------------------ multi-critic PPO (rl/multi_critic.py)
+    def _mc_batches(self):
+        """the minibatches with the K-wide values / returns in the scalar columns' places"""
+        return self.multi_critic.mini_batch_generator(self.storage, self.num_mini_batches, self.num_learning_epochs)
+
+    def _update_mc(self):
+        """update() with reward groups on: the captured step, the eager device one or the CPU one below, on the plain minibatch"""
+        mc = self.multi_critic
+        mc.head_sum.zero_()
+        if self._device_lr:
+            with self._blas_for_update():
+                out = self._update_graphed() if self._use_graph else self._update_device()
+        else:
+            out = self._update_mc_cpu()
+        mc.mean_head_losses = [h / self.num_updates for h in mc.head_sum.tolist()]   # one extra 4 K-byte read-back per update
+        return out
+
+    def _update_mc_cpu(self):
+        """update()'s CPU loop -- host-side adaptive learning rate, NaN-skip, clip and Adam -- on the K-wide minibatches"""
+        adaptive = self.desired_kl is not None and self.schedule == "adaptive"
+        mean_value_loss, mean_surrogate_loss = 0.0, 0.0
+        for (obs, cobs, actions, target_values, advantages, returns, old_logp, old_mu, old_sigma, _, _) in self._mc_batches():
+            surrogate_loss, value_loss, loss, kl_mean = self._losses(obs, cobs, actions, target_values, advantages, returns,
+                                                                     old_logp, old_mu, old_sigma)
+            if adaptive:
+                self._apply_kl(kl_mean.item())
+            if not torch.isfinite(loss):
+                continue
+            self.optimizer.zero_grad()
+            loss.backward()
+            if not torch.isfinite(nn.utils.clip_grad_norm_(self.actor_critic.parameters(), self.max_grad_norm)):
+                continue   # (a gradient whose norm is not finite skips the step too: include/grx_ppo.h grx_ppo_step_tail)
+            self.optimizer.step()
+            mean_value_loss += value_loss.item()
+            mean_surrogate_loss += surrogate_loss.item()
+        self.num_updates = self.num_learning_epochs * self.num_mini_batches
+        return mean_value_loss / self.num_updates, mean_surrogate_loss / self.num_updates
+
     def _update_device(self):
         """Same arithmetic as update(), no host round-trips inside the minibatch loop."""
         ac, multi = self.actor_critic, _collective_path()
         adaptive = self.desired_kl is not None and self.schedule == "adaptive"
         sums = torch.zeros(3, device=self.device)        # value loss, surrogate loss, last KL
         losses = self._losses if self.grad_penalty_coef is None else self._losses_gp
-        for (obs, cobs, actions, target_values, advantages, returns, old_logp, old_mu, old_sigma, _, _) in \
-                self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs):
+        batches = self._mc_batches() if self.multi_critic is not None else \
+            self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs)
+        for (obs, cobs, actions, target_values, advantages, returns, old_logp, old_mu, old_sigma, _, _) in batches:
             surrogate_loss, value_loss, loss, kl_mean = losses(obs, cobs, actions, target_values, advantages, returns,
                                                                old_logp, old_mu, old_sigma)
             if multi:
@@ -1110,6 +1203,8 @@ class PPO:
         st, dev = self.storage, self.device
         widths = [st.observations.shape[-1], (st.pri_observations if st.pri_observations is not None else st.observations).shape[-1],
                   st.actions.shape[-1], 1, 1, 1, 1, st.mu.shape[-1], st.sigma.shape[-1]]
+        if self.multi_critic is not None:   # (the stored values and the returns are K wide)
+            widths[3] = widths[5] = self.multi_critic.K
         rows = [mb] * len(widths) if self.symmetry is None else [mb * (2 if m else 1) for m in self._sym_modes]   # (symmetry: the mirrored half behind)
         if self.smooth is not None:   # (smoothness: the successor / perturbed rows behind the actor's input, eps and valid beside the batch)
             rows[0] = mb * self._smooth_rows()
@@ -1198,6 +1293,9 @@ class PPO:
         flat = lambda x: x.flatten(0, 1)
         cobs = st.pri_observations if st.pri_observations is not None else st.observations
         srcs = [flat(x) for x in (st.observations, cobs, st.actions, st.values, st.advantages, st.returns, st.actions_log_prob, st.mu, st.sigma)]
+        if self.multi_critic is not None:   # (the two K-wide tensors in the scalar value and return columns' places)
+            srcs[3], srcs[5] = flat(self.multi_critic.values), flat(self.multi_critic.returns)
+            self.multi_critic.head_sum.zero_()   # (the dry runs of a capture added to it)
         indices = torch.randperm(self.num_mini_batches * mb, requires_grad=False, device=self.device)   # RS:63-112: one permutation, reused
         self._sums.zero_()
         if self.symmetry is not None:

@@ -90,6 +90,7 @@ class OnPolicyRunner:
         # PPO's update.  Not config keys either (`--rnd` / `--rnd_*` or assignments to train_cfg.algorithm set them): without `rnd` nothing of
         # rl/rnd.py is constructed.  The algorithm's own keyword arguments are what is left
         rnd_cfg = {k[len("rnd_"):]: v for k, v in self.algorithm_cfg.items() if k.startswith("rnd_")} if self.algorithm_cfg.get("rnd") else None
+        self._rnd_requested = rnd_cfg is not None
         self.algorithm_cfg = {k: v for k, v in self.algorithm_cfg.items() if k != "rnd" and not k.startswith("rnd_")}
         self.rnd = None
         if rnd_cfg is not None:
@@ -135,6 +136,14 @@ class OnPolicyRunner:
             self.layer_norm = {"enabled": True, "eps": float(self.policy_cfg.get("layer_norm_eps", 1e-5))}
         else:
             self.policy_cfg = {k: v for k, v in self.policy_cfg.items() if k not in ("layer_norm", "layer_norm_eps")}
+        # multi-critic PPO: a value head, a GAE pass and an advantage normalisation per group of reward terms.  Not config
+        # keys either (`--reward_groups` / `--reward_group_weights` or assignments to train_cfg.algorithm set them): without `reward_groups`
+        # nothing of rl/multi_critic.py is imported
+        self.multi_critic = None   # the "multi_critic" entry of a checkpoint of this run: only under the flag
+        if self.algorithm_cfg.get("reward_groups") is not None:   # (an empty spec is refused by the parser, not taken for "no flag")
+            self._check_multi_critic(env)
+        else:
+            self.algorithm_cfg = {k: v for k, v in self.algorithm_cfg.items() if k not in ("reward_groups", "reward_group_weights")}
         self.estimator = None
         estimator_cfg = self._check_estimator(env) if bool(self.cfg.get("estimator", False)) else None
         if self.distill_from is not None:
@@ -176,6 +185,9 @@ class OnPolicyRunner:
             self.algorithm = _ALGORITHMS[self.cfg["algorithm_class_name"]](actor_critic=actor_critic, device=device, **self.algorithm_cfg, **extra)
             if self.privileged_actor:
                 self._alt_inputs = self._privileged_inputs
+            if self.multi_critic is not None:   # the step kernel's per-term tables, zero-copy views the rollout's store reads every step
+                base = env._sim.tensor("BASE_REWARD_TERMS") if self.algorithm.multi_critic.groups.uses_base else None
+                self.algorithm.multi_critic.bind_tables(env._sim.tensor("REWARD_TERMS"), base)
             if rnd_cfg is not None:   # (after the policy: its initial parameters are those of a run without the flag)
                 from .rnd import RandomNetworkDistillation
                 state = rnd_cfg.get("state", "privileged")
@@ -482,6 +494,50 @@ class OnPolicyRunner:
         if self.policy_cfg.get("activation", "elu") != "elu":
             raise ValueError(f"--layer_norm needs the elu activation, not {self.policy_cfg.get('activation')!r}: the fused pass is LayerNorm + ELU")
 
+    def _check_multi_critic(self, env):
+        """what --reward_groups needs of the env and does not combine with; parses the spec against the env's active terms and hands PPO
+        the parsed groups, the weights and a critic with one output per group"""
+        from .. import _capi
+        from .multi_critic import parse_reward_groups, parse_weights
+        why = "the per-group critic, GAE and value loss cover the plain fp32 MLP policy on the plain minibatch"
+        if self.recurrent:
+            raise ValueError(f"--reward_groups and --recurrent exclude each other: {why}")
+        if self.value_norm is not None:
+            raise ValueError("--reward_groups and --value_norm exclude each other: return statistics per value head are not implemented")
+        if self.symmetry is not None:
+            raise ValueError(f"--reward_groups and --symmetry exclude each other: {why}")
+        if self.smooth is not None:
+            raise ValueError(f"--reward_groups and --smooth exclude each other: {why}")
+        if self.grad_penalty_coef is not None:
+            raise ValueError(f"--reward_groups and --grad_penalty_coef exclude each other: {why}")
+        if self.state_dependent_std:
+            raise ValueError("--reward_groups and --state_dependent_std exclude each other: the multi-critic loss takes one sigma per action")
+        if self._rnd_requested:
+            raise ValueError("--reward_groups and --rnd exclude each other: the intrinsic reward belongs to no group")
+        if bool(self.cfg.get("estimator", False)):
+            raise ValueError("--reward_groups and --estimator exclude each other: the combination is not pinned")
+        if self.layer_norm is not None:
+            raise ValueError(f"--reward_groups and --layer_norm exclude each other: {why}")
+        if self.algorithm_cfg.get("precision", "fp32") == "bf16":
+            raise ValueError(f"--reward_groups and --precision bf16 exclude each other: {why}")
+        if self.distill_from is not None:
+            raise ValueError("--reward_groups and --distill_from exclude each other: a distillation run has no critic to split")
+        if bool(self.cfg.get("exact_resume", False)):
+            raise NotImplementedError("--reward_groups with --exact_resume is not implemented: a resumed multi-critic run is not pinned bit for bit")
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("--reward_groups with a world size above 1 is not implemented: the advantage statistics are per process")
+        if not bool(getattr(env.cfg.env, "publish_reward_terms", True)):
+            raise ValueError("--reward_groups needs an env built with env_cfg.env.publish_reward_terms = True (scripts/train.py sets it before "
+                             "make_env): the group rewards are sums over the step kernel's per-term reward tables")
+        if bool(env.cfg.rewards.only_positive_rewards):
+            raise ValueError("--reward_groups and rewards.only_positive_rewards = True exclude each other: with the clip the groups no longer add "
+                             "up to the env's reward")
+        groups = parse_reward_groups(self.algorithm_cfg["reward_groups"], list(env.reward_scales), _capi.REWARD_TERMS, _capi.BASE_REWARD_TERMS)
+        weights = parse_weights(self.algorithm_cfg.get("reward_group_weights"), groups.K)
+        self.algorithm_cfg = {**self.algorithm_cfg, "reward_groups": groups, "reward_group_weights": weights}
+        self.policy_cfg = {**self.policy_cfg, "num_critic_outputs": groups.K}
+        self.multi_critic = groups.entry(weights)
+
     def _check_value_norm(self):
         """what --value_norm does not combine with"""
         modes = ("running", "popart")   # (rl.value_norm.MODES)
@@ -624,6 +680,11 @@ class OnPolicyRunner:
                 w.add_scalar("Train/rnd_weight", self.rnd.weight(it), it)
             if self.estimator is not None:
                 w.add_scalar("Loss/estimator", locs["mean_estimator_loss"], it)
+            if self.multi_critic is not None:   # (Loss/value_function above is the sum over the heads)
+                spread = alg.multi_critic.stats[:, 1].tolist()   # the raw advantages' std per group, before normalisation
+                for k, name in enumerate(alg.multi_critic.groups.names):
+                    w.add_scalar("Loss/value_function_" + name, alg.multi_critic.mean_head_losses[k], it)
+                    w.add_scalar("Train/adv_std_" + name, spread[k], it)
             if self.value_norm is not None:   # (Loss/value_function above is in normalised units then)
                 w.add_scalar("Train/value_norm_mean", alg.value_norm.mean.item(), it)
                 w.add_scalar("Train/value_norm_std", alg.value_norm.std.item(), it)
@@ -685,6 +746,9 @@ class OnPolicyRunner:
             saved["value_norm"] = self.algorithm.value_norm.checkpoint()
         if self.layer_norm is not None:   # (likewise): that the hidden layers are Linear -> LayerNorm -> ELU, and the LayerNorms' eps
             saved["layer_norm"] = dict(self.layer_norm)
+        if self.multi_critic is not None:   # (likewise): the groups' names and terms, the weights
+            saved["multi_critic"] = {"groups": {n: list(t) for n, t in self.multi_critic["groups"].items()},
+                                     "weights": list(self.multi_critic["weights"])}
         torch.save(saved, path)
         if self.exact_resume:
             torch.save(self._train_state(), train_state_path(path))
@@ -786,6 +850,17 @@ class OnPolicyRunner:
                 raise ValueError(f"{path} was saved with value_norm={theirs!r}, this runner has value_norm={self.value_norm!r}: the critic's "
                                  f"output would not be in the units it was trained in (pass {want}, or set train_cfg.algorithm.value_norm, to "
                                  "match the checkpoint)")
+            if _groups_key(loaded.get("multi_critic")) != _groups_key(self.multi_critic):   # (before any load_state_dict: its size error would not name the flag)
+                theirs = loaded.get("multi_critic")
+                want = ("--reward_groups \"" + ";".join(n + "=" + ",".join(t) for n, t in theirs["groups"].items()) + "\" --reward_group_weights "
+                        + ",".join(str(x) for x in theirs["weights"])) if theirs is not None else "no --reward_groups"
+                raise ValueError(f"{path} was saved with multi_critic={theirs}, this runner has multi_critic={self.multi_critic}: the critic's "
+                                 f"heads would not be the ones that were trained (pass {want}, or set train_cfg.algorithm.reward_groups / "
+                                 "reward_group_weights, to match the checkpoint)")
+        elif _groups_key(loaded.get("multi_critic")) != _groups_key(self.multi_critic):   # (the actor alone is used: the critic and the optimizer stay what they are)
+            mine = self.algorithm.actor_critic.state_dict()
+            loaded["model_state_dict"] = {k: (mine[k] if k.startswith("critic.") else v) for k, v in loaded["model_state_dict"].items()}
+            load_optimizer = False
         saved_hist = loaded.get("obs_history", {"actor": 1, "critic": 1})   # (a checkpoint without the key: no history)
         if "distillation" in loaded and self.distillation is None:
             return self._load_student(path, loaded, saved_hist)
@@ -898,6 +973,11 @@ class OnPolicyRunner:
                 inner = NormalizedPolicy(inner, self.obs_normalizer)
             policy = HistoryPolicy(inner, self.env.num_obs, self.obs_history_length).to(device if device is not None else self.device)
         return policy
+
+
+def _groups_key(entry):
+    """a checkpoint's "multi_critic" entry as something to compare: the groups IN ORDER (a group's position is its value head), the weights"""
+    return None if entry is None else ([(n, list(t)) for n, t in entry["groups"].items()], [float(w) for w in entry["weights"]])
 
 
 def train_state_path(model_path):

@@ -10,6 +10,7 @@
     python -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless --value_norm popart                    (value normalisation, running or PopArt: DESIGN.md 4.16)
     python -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless --grad_penalty_coef 0.002              (a Lipschitz gradient penalty on the policy: DESIGN.md 4.17)
     python -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless --layer_norm                           (Linear -> LayerNorm -> ELU hidden layers: DESIGN.md 4.18)
+    python -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless --reward_groups "track=cmd_diff_lin_vel_x,cmd_diff_lin_vel_y,cmd_diff_ang_vel_yaw;rest=*"   (a critic per reward group: DESIGN.md 4.19)
     torchrun --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless
 """
 import os
@@ -22,7 +23,11 @@ from wiki_grx_gym_amd.utils import get_args, task_registry
 
 
 def train(args):
-    env, env_cfg = task_registry.make_env(name=args.task, args=args)
+    env_cfg = None
+    if getattr(args, "reward_groups", None) is not None:   # the group rewards are sums over the step kernel's per-term reward tables
+        env_cfg, _ = task_registry.get_cfgs(args.task)
+        env_cfg.env.publish_reward_terms = True
+    env, env_cfg = task_registry.make_env(name=args.task, args=args, env_cfg=env_cfg)
     ppo_runner, train_cfg = task_registry.make_alg_runner(env=env, name=args.task, args=args)
     ppo_runner.learn(num_learning_iterations=train_cfg.runner.max_iterations, init_at_random_ep_len=True)
 

@@ -126,6 +126,12 @@ def get_args(argv=None):
     p.add_argument("--layer_norm", action="store_true", default=False,
                    help="Layer normalisation in the actor's and the critic's hidden layers: Linear -> LayerNorm -> ELU (needs the elu "
                         "activation).  Saved in the checkpoint; --resume and play need the same flag")
+    p.add_argument("--reward_groups", type=str,
+                   help="Multi-critic PPO: `name=term,term,...;name=...` splits the task's active reward terms into 1..8 groups (`*` in one "
+                        "group: every term not named elsewhere); the critic gets a value head per group, GAE and the advantage "
+                        "normalisation run per group.  Saved in the checkpoint; --resume needs the same spec")
+    p.add_argument("--reward_group_weights", type=str,
+                   help="Weights `w1,...,wK` of --reward_groups' normalised group advantages in their sum (default all 1.0, not tuned)")
     args = p.parse_args(argv)
     if args.obs_history < 1 or args.critic_obs_history < 1:
         raise ValueError(f"--obs_history and --critic_obs_history must be >= 1, got {args.obs_history} and {args.critic_obs_history}")
@@ -214,6 +220,10 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
             cfg_train.policy.state_dependent_std = True
         if getattr(args, "layer_norm", False):   # (likewise)
             cfg_train.policy.layer_norm = True
+        if getattr(args, "reward_groups", None) is not None:   # (likewise; the weights travel only with --reward_groups)
+            cfg_train.algorithm.reward_groups = args.reward_groups
+            if getattr(args, "reward_group_weights", None) is not None:
+                cfg_train.algorithm.reward_group_weights = args.reward_group_weights
     return env_cfg, cfg_train
 
 
