@@ -295,4 +295,7 @@ int grx_rnd_reward(int N, int E, const float* pred, const float* targ, float gam
 /* ... and multi-critic PPO: a value head, a GAE pass and a value loss per group of reward terms,
  * csrc/grx_ppo_mc.hip in the same library */
 #include "grx_ppo_mc.h"
+/* ... and a Beta action distribution: the loss, the parameter map and the rollout's sample for an actor whose output
+ * layer is [p | q], csrc/grx_ppo_beta.hip in the same library */
+#include "grx_ppo_beta.h"
 #endif

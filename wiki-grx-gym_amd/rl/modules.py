@@ -282,12 +282,34 @@ class ActorCriticMLP(nn.Module):
                  critic_hidden_dims=(256, 256, 256), activation="elu", fixed_std=False, init_noise_std=1.0,
                  set_std=True, set_noise_std=1.0, actor_output_activation=None, critic_output_activation=None, actor_output_gain=1.0,
                  noise_std_type="scalar", state_dependent_std=False, layer_norm=False, layer_norm_eps=1e-5, num_critic_outputs=1,
-                 **kwargs):
+                 action_dist="gaussian", action_bounds=None, **kwargs):
         if kwargs:
             print("ActorCritic.__init__ got unexpected arguments, which will be ignored: " + str(list(kwargs)))
         if noise_std_type not in NOISE_STD_TYPES:
             raise ValueError(f"noise_std_type must be one of {NOISE_STD_TYPES}, not {noise_std_type!r}")
         state_dependent_std = bool(state_dependent_std)
+        # action_dist="beta" (rl/beta.py): the output layer is [p | q], the policy a Beta on the action box `action_bounds` =
+        # (lo, hi); "gaussian" builds the module exactly as before and imports nothing of rl/beta.py
+        if action_dist not in ("gaussian", "beta"):
+            raise ValueError(f"action_dist must be 'gaussian' or 'beta', not {action_dist!r}")
+        beta_dist = action_dist == "beta"
+        if beta_dist:
+            if noise_std_type != "scalar":
+                raise ValueError(f"--action_dist beta and --noise_std_type {noise_std_type} exclude each other: a Beta policy has no noise parameter")
+            if state_dependent_std:
+                raise ValueError("--action_dist beta and --state_dependent_std exclude each other: a Beta policy has no sigma to emit")
+            if fixed_std:
+                raise ValueError("--action_dist beta and fixed_std exclude each other: a Beta policy has no std parameter to fix")
+            if actor_output_activation is not None:
+                raise ValueError(f"--action_dist beta and actor_output_activation={actor_output_activation!r} exclude each other: the output "
+                                 "layer is [p | q], an activation on it is not defined")
+            if layer_norm:
+                raise ValueError("--action_dist beta and --layer_norm exclude each other: the combination is not pinned")
+            if int(num_critic_outputs) != 1:
+                raise ValueError("--action_dist beta and --reward_groups exclude each other: the multi-critic loss is a Gaussian policy's")
+            if action_bounds is None:
+                raise ValueError("action_dist='beta' needs action_bounds=(lo, hi), one value or one per action each (the runner takes them "
+                                 "from env.cfg.normalization.clip_actions_min / clip_actions_max, or --action_bounds)")
         if state_dependent_std and actor_output_activation is not None:
             raise ValueError(f"state_dependent_std with actor_output_activation={actor_output_activation!r}: the output layer is [mean | s], "
                              "an activation on it is not defined")
@@ -304,7 +326,9 @@ class ActorCriticMLP(nn.Module):
         # built exactly as before
         self.layer_norm = bool(layer_norm)
         ln = {"layer_norm": True, "layer_norm_eps": layer_norm_eps} if self.layer_norm else {}
-        self.actor = MLP(actor_num_input, 2 * actor_num_output if state_dependent_std else actor_num_output, actor_hidden_dims, activation, **ln)
+        self.action_dist = action_dist
+        wide = state_dependent_std or beta_dist   # (a 2A-wide output layer: [mean | s], or [p | q])
+        self.actor = MLP(actor_num_input, 2 * actor_num_output if wide else actor_num_output, actor_hidden_dims, activation, **ln)
         self.critic = MLP(critic_num_input, self.num_critic_output, critic_hidden_dims, activation, **ln)
         A = actor_num_output
         init = torch.as_tensor(init_noise_std, dtype=torch.float32) * torch.ones(A)
@@ -316,9 +340,23 @@ class ActorCriticMLP(nn.Module):
             with torch.no_grad():
                 last.weight[A:].zero_()
                 last.bias[A:].copy_(torch.log(init + 1e-7) if noise_std_type == "log" else init)
+        if beta_dist:   # the q rows get the gain too; the biases put the initial policy's mode at the zero action, its spread at init_noise_std
+            from .beta import _bounds, init_biases
+            lo, hi = _bounds(action_bounds[0], action_bounds[1], A, "action_bounds")
+            lo, span = torch.tensor(lo, dtype=torch.float64), torch.tensor(hi, dtype=torch.float64) - torch.tensor(lo, dtype=torch.float64)
+            with torch.no_grad():
+                if actor_output_gain != 1.0:
+                    last.weight[A:].mul_(float(actor_output_gain))
+                last.bias.copy_(init_biases(lo.numpy(), span.numpy(), init.double().numpy()))
+            # (buffers of the module: they travel in the state dict, and with the mean head into the exported policy)
+            self.register_buffer("action_lo", lo.float())
+            self.register_buffer("action_span", span.float())
+            self._alpha = self._beta = self.unit_actions = None
         self.fixed_std, self.init_noise_std = fixed_std, init_noise_std
         # (a number, as in the reference -- actor_critic_mlp.py -- or one value per action: the 32-DOF task starts its upper-body joints quieter)
-        if not state_dependent_std and noise_std_type == "log":
+        if beta_dist:
+            pass   # (no noise parameter)
+        elif not state_dependent_std and noise_std_type == "log":
             self.log_std = nn.Parameter(torch.log(init))
         elif not state_dependent_std:
             self.std = nn.Parameter(init.clone())
@@ -334,6 +372,8 @@ class ActorCriticMLP(nn.Module):
         """the [A] sigma as the loss differentiates it: `std`, exp(`log_std`), or the init_noise_std buffer under fixed_std"""
         if self.state_dependent_std:
             raise RuntimeError("state_dependent_std: sigma is a function of the state (the actor's second output half), there is no [A] sigma")
+        if self.action_dist == "beta":
+            raise RuntimeError("action_dist='beta': the policy has no noise parameter (action_std is the Beta's own spread)")
         if self.fixed_std:
             return self.init_std
         return torch.exp(self.log_std) if self.noise_std_type == "log" else self.std
@@ -346,12 +386,15 @@ class ActorCriticMLP(nn.Module):
 
     def inference_actor(self):
         """the module whose output is the mean action: `actor`, or its first A outputs under state_dependent_std"""
+        if self.action_dist == "beta":   # (the Beta's mean in action units; lo / span travel with the head)
+            from .beta import BetaMeanHead
+            return BetaMeanHead(self.actor, self.num_actor_output, self.action_lo, self.action_span)
         return MeanHead(self.actor, self.num_actor_output) if self.state_dependent_std else self.actor
 
     def assign_noise_std(self, std):
         """sigma := std [A] in place, whichever parameter holds it (a distilled student's fixed noise into an ordinary policy)"""
-        if self.state_dependent_std:
-            raise RuntimeError("state_dependent_std: there is no noise parameter to set")
+        if self.state_dependent_std or self.action_dist == "beta":
+            raise RuntimeError("state_dependent_std / action_dist='beta': there is no noise parameter to set")
         with torch.no_grad():
             if self.noise_std_type == "log":
                 self.log_std.copy_(torch.log(std))
@@ -360,7 +403,7 @@ class ActorCriticMLP(nn.Module):
 
     def load_state_dict(self, state_dict, strict=True):
         state_dict = dict(state_dict)
-        if self.state_dependent_std:   # (no noise parameter: nothing to overwrite)
+        if self.state_dependent_std or self.action_dist == "beta":   # (no noise parameter: nothing to overwrite)
             return super().load_state_dict(state_dict, strict)
         if self.noise_std_type == "log":   # (the reference's set_std / set_noise_std overwrite belongs to `std`: a log_std loads as saved)
             if self.fixed_std:
@@ -393,17 +436,34 @@ class ActorCriticMLP(nn.Module):
 
     @property
     def action_mean(self):
+        if self.action_dist == "beta":   # (in action units, for logging)
+            from .beta import mean_torch
+            return mean_torch(self._alpha, self._beta, self.action_lo, self.action_span)
         return self.distribution.mean
 
     @property
     def action_std(self):
+        if self.action_dist == "beta":   # (likewise)
+            from .beta import std_torch
+            return std_torch(self._alpha, self._beta, self.action_span)
         return self.distribution.stddev
 
     @property
     def entropy(self):
+        if self.action_dist == "beta":   # (of x, in unit-box coordinates: sum log span is left out, as in the log-probability)
+            from .beta import entropy_torch
+            return entropy_torch(self._alpha, self._beta)
         return self.distribution.entropy().sum(dim=-1)
 
+    def beta_params(self):
+        """(alpha, beta) of the last update_distribution under action_dist='beta'"""
+        return self._alpha, self._beta
+
     def update_distribution(self, observations):
+        if self.action_dist == "beta":
+            from .beta import params_torch
+            self._alpha, self._beta = params_torch(self.actor(observations))
+            return
         if self.state_dependent_std:
             mean, std = self.split_raw(self.actor(observations))
             self.distribution = Normal(mean, std)
@@ -414,12 +474,23 @@ class ActorCriticMLP(nn.Module):
 
     def act(self, observations, **_):
         self.update_distribution(observations)
+        if self.action_dist == "beta":   # the env's action; `unit_actions` keeps x, which is what the storage and get_actions_log_prob take
+            from .beta import sample_torch
+            with torch.no_grad():
+                self.unit_actions, actions, _ = sample_torch(self._alpha.detach(), self._beta.detach(), self.action_lo, self.action_span)
+            return actions
         return self.distribution.sample()
 
     def get_actions_log_prob(self, actions):
+        if self.action_dist == "beta":   # (`actions` in unit-box coordinates: x, not lo + span x)
+            from .beta import logp_torch
+            return logp_torch(self._alpha, self._beta, actions)
         return self.distribution.log_prob(actions).sum(dim=-1)
 
     def act_inference(self, observations):
+        if self.action_dist == "beta":
+            from .beta import mean_torch, params_torch
+            return mean_torch(*params_torch(self.actor(observations)), self.action_lo, self.action_span)
         if self.state_dependent_std:
             return self.actor(observations)[..., :self.num_actor_output]
         return self.actor(observations)

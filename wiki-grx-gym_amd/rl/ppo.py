@@ -136,6 +136,12 @@ class PPO:
             if _world() > 1:
                 raise NotImplementedError("PPO: --state_dependent_std with a world size above 1 is not implemented: it trains in one "
                                           "process only")
+        # a Beta action distribution (rl/beta.py): the actor's output is [p | q], the storage holds x in unit-box coordinates
+        # and alpha / beta in mu / sigma's rows, the loss is grx_ppo_loss_beta; the minibatch step is captured as the default is, the
+        # rollout's policy step runs eagerly (two torch gamma draws).  None of rl/beta.py is imported without it
+        self._beta = getattr(actor_critic, "action_dist", "gaussian") == "beta"
+        if self._beta:
+            self._init_beta(symmetry, smooth, grad_penalty_coef, reward_groups)
         if self._recurrent:
             if _world() > 1:
                 raise NotImplementedError("PPO: a recurrent policy trains in one process only")
@@ -230,6 +236,51 @@ class PPO:
         # the nine minibatch tensors (obs, cobs, actions, values, advantages, returns, old_logp, old_mu, old_sigma): how each gets its second half
         self._sym_modes = [2, 2, 2, 1, 1, 1, 1, 2, 2] if symmetry in ("augment", "both") else [2, 0, 0, 0, 0, 0, 0, 0, 0]
         self._sym_tensor_maps = [maps.obs, maps.cobs, maps.actions, None, None, None, None, maps.actions, maps.sigma]
+
+    def _init_beta(self, symmetry, smooth, grad_penalty_coef, reward_groups):
+        """what --action_dist beta does not combine with in PPO (the runner refuses the rest: it owns those options)"""
+        why = "the Beta policy's loss, rollout step and storage cover the plain fp32 MLP policy on the plain minibatch"
+        if self._recurrent:
+            raise ValueError(f"PPO: --action_dist beta and --recurrent exclude each other: {why}")
+        if symmetry is not None:
+            raise ValueError("PPO: --action_dist beta and --symmetry exclude each other: a mirror map of the [p | q] output is not implemented")
+        if smooth is not None:
+            raise ValueError("PPO: --action_dist beta and --smooth exclude each other: a smoothness loss on the [p | q] output is not implemented")
+        if grad_penalty_coef is not None:
+            raise ValueError(f"PPO: --action_dist beta and --grad_penalty_coef exclude each other: the penalty differentiates a Gaussian's "
+                             f"log-probability; {why}")
+        if reward_groups is not None:
+            raise ValueError("PPO: --action_dist beta and --reward_groups exclude each other: the multi-critic loss is a Gaussian policy's")
+        if getattr(self.actor_critic, "layer_norm", False):
+            raise ValueError("PPO: --action_dist beta and --layer_norm exclude each other: the combination is not pinned")
+        if self.precision == "bf16":
+            raise ValueError(f"PPO: --action_dist beta and --precision bf16 exclude each other: {why}")
+        if _world() > 1:
+            raise NotImplementedError("PPO: --action_dist beta with a world size above 1 is not implemented: it trains in one process only")
+        if self.actor_critic.num_actor_output > 32:
+            raise ValueError(f"PPO: --action_dist beta covers 1..32 actions (include/grx_ppo_beta.h), not {self.actor_critic.num_actor_output}")
+        self._use_act_graph = False   # the rollout's policy step draws from torch's gamma sampler: eager (DESIGN.md 4.20)
+        from .beta import fused_enabled
+        if self._use_graph and not fused_enabled():   # (the torch spelling is not what the captured step is pinned on)
+            print("PPO: GRX_BETA_FUSED=0 -> the minibatch step runs eagerly (GRX_PPO_GRAPH=0)")
+            self._use_graph = self._two_streams = False
+
+    def _act_beta(self, actor_observations, critic_observations):
+        """act() for a Beta policy: (x, values, logp, alpha, beta, a).  On a HIP device the actor's raw output through the inference forward
+        (fused_loss.mlp_forward), grx_beta_params, two torch._standard_gamma draws, grx_beta_sample; elsewhere the torch spelling"""
+        from . import beta as B
+        ac = self.actor_critic
+        with torch.no_grad():
+            on_hip = actor_observations.is_cuda and not torch.is_grad_enabled()
+            fuse = (on_hip and os.environ.get("GRX_PPO_FUSED_MLP", "1") != "0" and mlp_can_fuse(ac.actor, actor_observations)
+                    and mlp_can_fuse(ac.critic, critic_observations))
+            raw = mlp_forward(ac.actor, actor_observations) if fuse else ac.actor(actor_observations)
+            values = mlp_forward(ac.critic, critic_observations) if fuse else ac.evaluate(critic_observations)
+            if self.value_norm is not None:   # (the network's output is a normalised value: the storage and GAE work in reward units)
+                values = self.value_norm.denormalize(values)
+            alpha, beta = B.beta_params(raw) if (raw.is_cuda and B.fused_enabled()) else B.params_torch(raw)
+            x, a, logp = B.rollout_sample(alpha, beta, ac.action_lo, ac.action_span)
+        return x, values, logp, alpha, beta, a
 
     def _init_layer_norm(self, grad_penalty_coef):
         if self._recurrent:
@@ -444,6 +495,11 @@ class PPO:
         t = self.transition
         if self._recurrent:
             return self._act_recurrent(actor_observations, critic_observations)
+        if self._beta:   # the storage takes x and (alpha, beta); the env takes a = lo + span x
+            t.actions, t.values, t.actions_log_prob, t.action_mean, t.action_sigma, env_actions = self._act_beta(actor_observations,
+                                                                                                              critic_observations)
+            t.observations, t.critic_observations = actor_observations, critic_observations
+            return env_actions
         if self._use_act_graph and actor_observations.is_cuda and not torch.is_grad_enabled():
             t.actions, t.values, t.actions_log_prob, t.action_mean, t.action_sigma = self._act_graphed(actor_observations, critic_observations)
         else:
@@ -570,6 +626,8 @@ class PPO:
             return self._update_gp()
         if self.multi_critic is not None:
             return self._update_mc()
+        if self._beta and not self._device_lr:   # (the CPU loop below spells out the Gaussian's KL)
+            return self._update_beta_cpu()
         if self._device_lr:
             # For these GEMM shapes (batch ~10^4 rows, 39..512 columns, fp32) rocBLAS's kernel choices beat hipBLASLt's by 2x
             # on the weight-gradient products dY^T X (27-48 us against 66-73 us, tools/gpu_gemm_probe.py).  torch's BLAS
@@ -692,6 +750,10 @@ class PPO:
 
     def _loss_is_fused(self):
         ac = self.actor_critic
+        if self._beta:   # (GRX_BETA_FUSED=0: the torch spelling on a HIP device too)
+            from .beta import fused_enabled
+            if not fused_enabled():
+                return False
         return self._fused_loss and not ac.fixed_std and ac.num_actor_output <= 32   # the kernel's action-count limit
 
     def _forward(self, obs, cobs, actor=None):
@@ -701,8 +763,8 @@ class PPO:
         if actor is not None:
             if not self._loss_is_fused():
                 return actor(obs), ac.evaluate(cobs)
-        elif self._state_dependent and not self._loss_is_fused():
-            return ac.actor(obs), ac.evaluate(cobs)   # (the raw output [mean | s]: _loss_terms splits it)
+        elif (self._state_dependent or self._beta) and not self._loss_is_fused():
+            return ac.actor(obs), ac.evaluate(cobs)   # (the raw output [mean | s] or [p | q]: _loss_terms splits it)
         elif not self._loss_is_fused():
             ac.update_distribution(obs)   # (the torch spelling in _loss_terms reads sigma from the distribution)
             return ac.action_mean, ac.evaluate(cobs)
@@ -735,6 +797,15 @@ class PPO:
             return self.multi_critic.loss(mu, _noise_std(ac), value, actions, old_logp, old_mu, old_sigma, advantages, returns, target_values,
                                           self.clip_param, self.value_loss_coef, self.entropy_coef, self.use_clipped_value_loss, adaptive,
                                           self._loss_is_fused())
+        if self._beta:   # (mu is the raw [p | q], actions are x, old_mu / old_sigma the rollout's alpha / beta)
+            from . import beta as B
+            if self._loss_is_fused():
+                out = B.fused_ppo_loss_beta(mu, value, actions, old_logp, old_mu, old_sigma, advantages, returns, target_values,
+                                            self.clip_param, self.value_loss_coef, self.entropy_coef, self.use_clipped_value_loss)
+                kl_mean = out[3].detach() if adaptive else torch.zeros((), device=self.device)
+                return out[0], out[1], out[2], kl_mean
+            return B.loss_torch(mu, value, actions, old_logp, old_mu, old_sigma, advantages, returns, target_values, self.clip_param,
+                                self.value_loss_coef, self.entropy_coef, self.use_clipped_value_loss, with_kl=adaptive)
         if self._state_dependent and self._loss_is_fused():   # (mu is the raw [mean | s]: the gradient lands on it in one launch)
             out = fused_ppo_loss_sd(mu, value, actions, old_logp, old_mu, old_sigma, advantages, returns, target_values,
                                     ac.noise_std_type == "log", self.clip_param, self.value_loss_coef, self.entropy_coef,
@@ -1066,6 +1137,28 @@ class PPO:
         self.num_updates = self.num_learning_epochs * self.num_mini_batches
         return mean_value_loss / self.num_updates, mean_surrogate_loss / self.num_updates
 
+    def _update_beta_cpu(self):
+        """update()'s CPU loop -- host-side adaptive learning rate, NaN-skip, clip and Adam -- around _losses for a Beta policy"""
+        adaptive = self.desired_kl is not None and self.schedule == "adaptive"
+        mean_value_loss, mean_surrogate_loss = 0.0, 0.0
+        for (obs, cobs, actions, target_values, advantages, returns, old_logp, old_mu, old_sigma, _, _) in \
+                self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs):
+            surrogate_loss, value_loss, loss, kl_mean = self._losses(obs, cobs, actions, target_values, advantages, returns,
+                                                                     old_logp, old_mu, old_sigma)
+            if adaptive:
+                self._apply_kl(kl_mean.item())
+            if not torch.isfinite(loss):
+                continue
+            self.optimizer.zero_grad()
+            loss.backward()
+            if not torch.isfinite(nn.utils.clip_grad_norm_(self.actor_critic.parameters(), self.max_grad_norm)):
+                continue   # (a gradient whose norm is not finite skips the step too: include/grx_ppo.h grx_ppo_step_tail)
+            self.optimizer.step()
+            mean_value_loss += value_loss.item()
+            mean_surrogate_loss += surrogate_loss.item()
+        self.num_updates = self.num_learning_epochs * self.num_mini_batches
+        return mean_value_loss / self.num_updates, mean_surrogate_loss / self.num_updates
+
     def _update_device(self):
         """Same arithmetic as update(), no host round-trips inside the minibatch loop."""
         ac, multi = self.actor_critic, _collective_path()
@@ -1215,6 +1308,8 @@ class PPO:
         ac_state = [p.detach().clone() for p in self.actor_critic.parameters()]   # (not load_state_dict: it rewrites std, AC:116-134)
         lr0 = self._lr_t.clone()
         self._static[8].fill_(1.0)   # sigma > 0 for the dry runs
+        if self._beta:   # (x inside the box, alpha = beta = 1 likewise)
+            self._static[2].fill_(0.5); self._static[7].fill_(1.0)
         # The GEMM kernels are chosen when the graph is captured.  For these shapes (batch ~10^4 rows, 39..512 columns,
         # fp32) rocBLAS's choices beat hipBLASLt's by 2x on the weight-gradient products dY^T X (27-48 us against
         # 66-73 us, tools/gpu_gemm_probe.py).  The preference is process-global in torch, so it is switched for the

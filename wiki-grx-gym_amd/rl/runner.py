@@ -105,6 +105,13 @@ class OnPolicyRunner:
             self.noise = {"std_type": self.noise_std_type, "state_dependent": self.state_dependent_std}
         if self.recurrent:
             self._check_recurrent()
+        # a Beta action distribution: the policy's support is the env's action box.  Not config keys either (`--action_dist`
+        # / `--action_bounds` or assignments to train_cfg.policy set them): with the default `gaussian` nothing of rl/beta.py is imported
+        self.action_dist = None   # the "action_dist" entry of a checkpoint of this run: only under the flag
+        if self.policy_cfg.get("action_dist", "gaussian") != "gaussian":
+            self._check_beta(env)
+        else:
+            self.policy_cfg = {k: v for k, v in self.policy_cfg.items() if k not in ("action_dist", "action_bounds")}
         # action smoothness: the CAPS regulariser on the actor's mean in PPO's update.  Not config keys either (`--smooth` /
         # `--smooth_*` or assignments to train_cfg.algorithm set them); nothing of it is saved
         self.smooth = self.algorithm_cfg.get("smooth") or None
@@ -608,6 +615,52 @@ class OnPolicyRunner:
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise NotImplementedError("--state_dependent_std with a world size above 1 is not implemented: it trains in one process only")
 
+    def _check_beta(self, env):
+        """what --action_dist beta does not combine with, and the action box: policy_cfg["action_bounds"] becomes (lo, hi) per joint"""
+        from .beta import ACTION_DISTS, resolve_bounds
+        kind = self.policy_cfg["action_dist"]
+        if kind not in ACTION_DISTS:
+            raise ValueError(f"--action_dist must be one of {ACTION_DISTS}, not {kind!r}")
+        why = "the Beta policy's loss, rollout step and storage cover the plain fp32 MLP policy of a PPO run in one process"
+        if self.noise_std_type != "scalar":
+            raise ValueError(f"--action_dist beta and --noise_std_type {self.noise_std_type} exclude each other: a Beta policy has no noise parameter")
+        if self.state_dependent_std:
+            raise ValueError("--action_dist beta and --state_dependent_std exclude each other: a Beta policy has no sigma to emit")
+        if self.recurrent:
+            raise ValueError(f"--action_dist beta and --recurrent exclude each other: {why}")
+        if self.symmetry is not None:
+            raise ValueError("--action_dist beta and --symmetry exclude each other: a mirror map of the [p | q] output is not implemented")
+        if self.algorithm_cfg.get("smooth"):
+            raise ValueError("--action_dist beta and --smooth exclude each other: a smoothness loss on the [p | q] output is not implemented")
+        if self.algorithm_cfg.get("grad_penalty_coef") is not None:
+            raise ValueError("--action_dist beta and --grad_penalty_coef exclude each other: the penalty differentiates a Gaussian's log-probability")
+        if self.algorithm_cfg.get("reward_groups") is not None:
+            raise ValueError("--action_dist beta and --reward_groups exclude each other: the multi-critic loss is a Gaussian policy's")
+        if self.distill_from is not None:
+            raise ValueError("--action_dist beta and --distill_from exclude each other: the student regresses a mean action under a fixed "
+                             "Gaussian noise")
+        if self._rnd_requested:
+            raise ValueError("--action_dist beta and --rnd exclude each other: the combination is not pinned")
+        if bool(self.cfg.get("estimator", False)):
+            raise ValueError("--action_dist beta and --estimator exclude each other: the combination is not pinned")
+        if bool(self.policy_cfg.get("layer_norm", False)):
+            raise ValueError("--action_dist beta and --layer_norm exclude each other: the combination is not pinned")
+        if self.algorithm_cfg.get("precision", "fp32") != "fp32":
+            raise ValueError(f"--action_dist beta and --precision {self.algorithm_cfg['precision']} exclude each other: {why}")
+        if bool(self.cfg.get("exact_resume", False)):
+            raise NotImplementedError("--action_dist beta with --exact_resume is not implemented: the eager rollout step's draws are not pinned "
+                                      "against an uninterrupted run")
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("--action_dist beta with a world size above 1 is not implemented: it trains in one process only")
+        if self.policy_cfg.get("fixed_std", False):
+            raise ValueError("--action_dist beta and fixed_std exclude each other: a Beta policy has no std parameter to fix")
+        if self.policy_cfg.get("actor_output_activation") is not None:
+            raise ValueError(f"--action_dist beta and actor_output_activation={self.policy_cfg['actor_output_activation']!r} exclude each other: "
+                             "the output layer is [p | q], an activation on it is not defined")
+        lo, hi = resolve_bounds(env.cfg.normalization, env.num_actions, self.policy_cfg.get("action_bounds"))
+        self.policy_cfg = dict(self.policy_cfg, action_bounds=(lo, hi))
+        self.action_dist = {"kind": kind, "lo": lo, "hi": hi}
+
     def _check_recurrent(self):
         """what a recurrent policy (--recurrent) does not combine with"""
         if self.obs_history_length != 1 or self.critic_obs_history_length != 1:
@@ -699,6 +752,10 @@ class OnPolicyRunner:
             w.add_scalar("Train/mean_episode_length/time", ml, self.tot_time)
         if self.state_dependent_std:   # per action, the mean over the rollout just trained on (clear_storage() keeps the rows)
             stds = alg.storage.sigma.detach().flatten(0, 1).mean(0)
+        elif self.action_dist is not None:   # the Beta's std in action units (ActorCriticMLP.action_std's formula), over the same rows
+            from .beta import std_torch
+            stds = std_torch(alg.storage.mu.detach().flatten(0, 1), alg.storage.sigma.detach().flatten(0, 1),
+                             alg.actor_critic.action_span).mean(0)
         elif self.distillation is not None:   # (a student's noise is a fixed buffer)
             stds = alg.actor_critic.std.detach()
         else:
@@ -738,6 +795,8 @@ class OnPolicyRunner:
             saved["recurrent"] = {"hidden_size": self.algorithm.actor_critic.rnn_hidden_size}
         if self.noise is not None:   # (likewise)
             saved["noise"] = dict(self.noise)
+        if self.action_dist is not None:   # (likewise): the kind and the action box
+            saved["action_dist"] = {k: (list(v) if isinstance(v, list) else v) for k, v in self.action_dist.items()}
         if self.rnd is not None:   # (likewise): both networks, RND's normaliser, the discounted-return state, the optimizer, the configuration
             saved["rnd"] = self.rnd.checkpoint()
         if self.estimator is not None:   # (likewise): the network, its optimizer, the targets and hidden layers
@@ -831,6 +890,13 @@ class OnPolicyRunner:
                              f"the one that was trained (pass --noise_std_type {want['std_type']}"
                              f"{' --state_dependent_std' if want['state_dependent'] else ' without --state_dependent_std'}, or set "
                              "train_cfg.policy.noise_std_type / train_cfg.policy.state_dependent_std, to match the checkpoint)")
+        if loaded.get("action_dist") != self.action_dist:   # (before any load_state_dict: its size error would not name the flag)
+            theirs = loaded.get("action_dist")
+            want = f"--action_dist {theirs['kind']} with the action box lo={theirs['lo']}, hi={theirs['hi']}" if theirs is not None \
+                else "--action_dist gaussian, the default"
+            raise ValueError(f"{path} was saved with action_dist={theirs}, this runner has action_dist={self.action_dist}: the policy would not be "
+                             f"the one that was trained (pass {want}, or set train_cfg.policy.action_dist / action_bounds, to match the "
+                             "checkpoint; the flag is --action_dist)")
         if loaded.get("layer_norm") != self.layer_norm:   # (before any load_state_dict: its key error would not name the flag)
             raise ValueError(f"{path} was saved with layer_norm={loaded.get('layer_norm')}, this runner has layer_norm={self.layer_norm}: the "
                              f"networks would not be the ones that were trained (pass {'--layer_norm' if 'layer_norm' in loaded else 'no --layer_norm'}"
@@ -930,7 +996,7 @@ class OnPolicyRunner:
     def _mean_actor(self):
         """the module whose output is the mean action: the actor, or the first A of its 2A outputs under state_dependent_std"""
         ac = self.algorithm.actor_critic
-        return ac.inference_actor() if self.state_dependent_std else ac.actor
+        return ac.inference_actor() if (self.state_dependent_std or self.action_dist is not None) else ac.actor
 
     def get_inference_policy(self, device=None):
         self.algorithm.actor_critic.eval()

@@ -10,6 +10,10 @@ RECORD_FRAMES and MOVE_CAMERA are out of scope.  Files under `exporte
   * `play_states.png` / `.json` -- `logger.plot_states()` at step `stop_state_log` (:128-129);
   * `play_rewards.json`  -- what `logger.log_rewards` accumulates and `print_rewards` shows (:131-137): per reward term, the
     episode means weighted by the number of episodes that ended, over the first `max_episode_length` steps.
+
+A checkpoint trained with `--action_dist beta` needs the same flag here (and `--action_bounds` where the run had them): they
+reach the runner through `get_args` / `make_alg_runner`, whose `load` refuses a mismatch; the policy and the exported module then act on
+the Beta's mean in action units.
 """
 import json
 import os

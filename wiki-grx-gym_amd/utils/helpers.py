@@ -132,6 +132,12 @@ def get_args(argv=None):
                         "normalisation run per group.  Saved in the checkpoint; --resume needs the same spec")
     p.add_argument("--reward_group_weights", type=str,
                    help="Weights `w1,...,wK` of --reward_groups' normalised group advantages in their sum (default all 1.0, not tuned)")
+    p.add_argument("--action_dist", type=str, choices=["gaussian", "beta"],
+                   help="The policy's action distribution: a Gaussian (default) or a Beta on the env's action box "
+                        "(normalization.clip_actions_min / clip_actions_max), which cannot sample outside it.  Saved in the checkpoint; "
+                        "--resume and play need the same value")
+    p.add_argument("--action_bounds", type=float, nargs=2, metavar=("LO", "HI"),
+                   help="The action box of --action_dist beta for a task whose config has only the scalar clip_actions (the same for every joint)")
     args = p.parse_args(argv)
     if args.obs_history < 1 or args.critic_obs_history < 1:
         raise ValueError(f"--obs_history and --critic_obs_history must be >= 1, got {args.obs_history} and {args.critic_obs_history}")
@@ -224,6 +230,10 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
             cfg_train.algorithm.reward_groups = args.reward_groups
             if getattr(args, "reward_group_weights", None) is not None:
                 cfg_train.algorithm.reward_group_weights = args.reward_group_weights
+        if getattr(args, "action_dist", None) is not None:   # (likewise: the policy config has no such keys otherwise)
+            cfg_train.policy.action_dist = args.action_dist
+        if getattr(args, "action_bounds", None) is not None:   # (likewise)
+            cfg_train.policy.action_bounds = [float(args.action_bounds[0]), float(args.action_bounds[1])]
     return env_cfg, cfg_train
 
 
@@ -264,6 +274,8 @@ def export_policy_as_jit(actor_critic, path, normalizer=None, history=1, estimat
     `history` > 1 (the runner's obs_history_length): it takes raw SINGLE frames and keeps the last `history` of them itself
     (rl.history.HistoryPolicy: `reset_memory()` and `reset(dones)` are exported methods).
     An actor_critic with `state_dependent_std`: the exported module returns the mean, the first A of the actor's 2A outputs.
+    An actor_critic with `action_dist="beta"`: the exported module returns the Beta's mean in action units, lo + span * alpha / (alpha + beta),
+    with lo / span as its own buffers (rl.beta.BetaMeanHead).
     `estimator` (the network of an rl.estimator.StateEstimator): behind history and normaliser the module appends the estimate to the
     actor's input itself (rl.estimator.EstimatorPolicy); a consumer still feeds raw single frames"""
     os.makedirs(path, exist_ok=True)
