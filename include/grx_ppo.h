@@ -298,4 +298,7 @@ int grx_rnd_reward(int N, int E, const float* pred, const float* targ, float gam
 /* ... and a Beta action distribution: the loss, the parameter map and the rollout's sample for an actor whose output
  * layer is [p | q], csrc/grx_ppo_beta.hip in the same library */
 #include "grx_ppo_beta.h"
+/* ... and the context-aided estimator network: the rollout's head behind the encoder, the reparameterisation with its
+ * backward, and the estimation + reconstruction + KL loss, csrc/grx_ppo_cenet.hip in the same library */
+#include "grx_ppo_cenet.h"
 #endif

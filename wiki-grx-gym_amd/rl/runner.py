@@ -153,6 +153,11 @@ class OnPolicyRunner:
             self.algorithm_cfg = {k: v for k, v in self.algorithm_cfg.items() if k not in ("reward_groups", "reward_group_weights")}
         self.estimator = None
         estimator_cfg = self._check_estimator(env) if bool(self.cfg.get("estimator", False)) else None
+        # a context-aided estimator network: the estimator's regression plus a stochastic latent that a decoder predicts the
+        # next frame from; [v_hat | z] is appended to the actor's input and both networks are trained after PPO's update.  Not config keys
+        # either (`--cenet` / `--cenet_*` or assignments to train_cfg.runner set them): without `cenet` nothing of rl/cenet.py is imported
+        self.cenet = None
+        cenet_cfg = self._check_cenet(env) if bool(self.cfg.get("cenet", False)) else None
         if self.distill_from is not None:
             teacher = self._check_distillation(env, device)
         self.obs_history = self.critic_obs_history = None
@@ -183,6 +188,8 @@ class OnPolicyRunner:
         else:
             # (with an estimator the policy acts on [x | est(x)]: E more columns; the normaliser's statistics stay actor_in wide)
             policy_in = actor_in + (len(estimator_cfg["cols"]) if estimator_cfg is not None else 0)
+            if cenet_cfg is not None:   # (likewise: [x | v_hat | z], E + Z more columns)
+                policy_in = actor_in + len(cenet_cfg["cols"]) + cenet_cfg["latent_dim"]
             actor_critic = policy_cls(policy_in, critic_in, env.num_actions, **self.policy_cfg).to(device)
             extra = {}
             if self.symmetry is not None:   # (a model the joint map refuses, an asymmetric height scan: build_maps' ValueError)
@@ -206,6 +213,10 @@ class OnPolicyRunner:
                 self.estimator = StateEstimator(actor_in, env.num_obs, env.num_pri_obs, env.num_envs, self.cfg["num_steps_per_env"], device,
                                                 targets=estimator_cfg["targets"], hidden_dims=estimator_cfg["hidden_dims"],
                                                 learning_rate=estimator_cfg["learning_rate"], num_epochs=estimator_cfg["num_epochs"])
+            if cenet_cfg is not None:   # (after the policy, as the estimator: its initial parameters are those of a run without the flag)
+                from .cenet import CENet
+                self.cenet = CENet(actor_in, env.num_obs, env.num_obs, env.num_pri_obs, env.num_envs, self.cfg["num_steps_per_env"], device,
+                                   **{k: v for k, v in cenet_cfg.items() if k != "cols"})
         self.alg = self.algorithm
         self.num_steps_per_env, self.save_interval = self.cfg["num_steps_per_env"], self.cfg["save_interval"]
         # exact resume: every save() also writes train_state_<it>.pt, the whole training state; not a config key
@@ -276,6 +287,8 @@ class OnPolicyRunner:
             obs = obs_n
         if self.estimator is not None:   # the last stage: [x | est(x)]; the frame's targets wait for the row's rollout step
             obs = self.estimator.step(obs, pri.to(self.device), None)
+        if self.cenet is not None:   # (likewise): [x | v_hat | z]
+            obs = self.cenet.step(obs, pri.to(self.device), None)
         alg.actor_critic.train()
         ep_infos = []
         if pending is None:
@@ -300,6 +313,8 @@ class OnPolicyRunner:
             with torch.inference_mode():
                 if self.estimator is not None:   # the row this rollout starts with was built from the frames parked last
                     self.estimator.begin_rollout()
+                if self.cenet is not None:
+                    self.cenet.begin_rollout()
                 for t_ in range(self.num_steps_per_env):
                     actions = alg.act(obs, critic_obs)
                     obs, pri, rewards, dones, infos = env.step(actions)
@@ -315,6 +330,8 @@ class OnPolicyRunner:
                         obs, critic_obs = self._normalize_step(obs, critic_obs if pri is not None else None)
                     if self.estimator is not None:   # this row is acted on at step t_ + 1: its targets are the raw privileged frame of this step
                         obs = self.estimator.step(obs, pri.to(self.device), t_ + 1 if t_ + 1 < self.num_steps_per_env else None)
+                    if self.cenet is not None:   # (likewise)
+                        obs = self.cenet.step(obs, pri.to(self.device), t_ + 1 if t_ + 1 < self.num_steps_per_env else None)
                     if self.log_dir is not None:
                         if "episode" in infos:
                             ep_infos.append(infos["episode"])
@@ -344,6 +361,8 @@ class OnPolicyRunner:
                     mean_intrinsic_reward = self.rnd.intrinsic.mean().item()
             if self.estimator is not None:   # the regression on this rollout: the stored rows' first columns against the stored targets
                 mean_estimator_loss = self.estimator.update(alg.storage.observations, alg.num_mini_batches)
+            if self.cenet is not None:   # estimation, reconstruction of the successor row's newest frame and KL, on this rollout
+                mean_cenet_losses = self.cenet.update(alg.storage.observations, alg.storage.dones, alg.num_mini_batches)
             alg.clear_storage()
             if self.sync_timers:
                 torch.cuda.synchronize()
@@ -523,6 +542,8 @@ class OnPolicyRunner:
             raise ValueError("--reward_groups and --rnd exclude each other: the intrinsic reward belongs to no group")
         if bool(self.cfg.get("estimator", False)):
             raise ValueError("--reward_groups and --estimator exclude each other: the combination is not pinned")
+        if bool(self.cfg.get("cenet", False)):
+            raise ValueError("--reward_groups and --cenet exclude each other: the combination is not pinned")
         if self.layer_norm is not None:
             raise ValueError(f"--reward_groups and --layer_norm exclude each other: {why}")
         if self.algorithm_cfg.get("precision", "fp32") == "bf16":
@@ -596,6 +617,53 @@ class OnPolicyRunner:
                 "hidden_dims": check_hidden_dims(self.cfg.get("estimator_hidden_dims", (128, 64))),
                 "learning_rate": float(self.cfg.get("estimator_learning_rate", 1e-3)), "num_epochs": int(self.cfg.get("estimator_num_epochs", 1))}
 
+    def _check_cenet(self, env):
+        """what --cenet does not combine with; returns CENet's options: targets, their columns, latent_dim, beta, encoder_dims,
+        decoder_dims, learning_rate, num_epochs"""
+        from .cenet import MAX_TARGETS, check_dims, check_layout, check_values, parse_targets, target_columns
+        pinned = "the combination is not pinned"
+        if bool(self.cfg.get("estimator", False)):
+            raise ValueError("--cenet and --estimator exclude each other: CENet contains the estimator (its v_hat head; pass --cenet_targets)")
+        if self.recurrent:
+            raise ValueError("--cenet and --recurrent exclude each other: the memory is the estimator")
+        if self.privileged_actor:
+            raise ValueError("--cenet and --privileged_actor exclude each other: the actor already reads the targets")
+        if self.distill_from is not None:
+            raise ValueError("--cenet and --distill_from exclude each other: a distillation run has no PPO update CENet trains beside")
+        if self.symmetry is not None:
+            raise ValueError("--cenet and --symmetry exclude each other: a mirror map of the appended columns is not implemented")
+        if self.smooth is not None:
+            raise ValueError("--cenet and --smooth exclude each other: the perturbed and successor rows would carry another draw of z")
+        if self.grad_penalty_coef is not None:
+            raise ValueError(f"--cenet and --grad_penalty_coef exclude each other: {pinned}")
+        if self.state_dependent_std:
+            raise ValueError(f"--cenet and --state_dependent_std exclude each other: {pinned}")
+        if self._rnd_requested:
+            raise ValueError(f"--cenet and --rnd exclude each other: {pinned}")
+        if self.layer_norm is not None:
+            raise ValueError(f"--cenet and --layer_norm exclude each other: {pinned}")
+        if self.multi_critic is not None:
+            raise ValueError(f"--cenet and --reward_groups exclude each other: {pinned}")
+        if self.action_dist is not None:
+            raise ValueError(f"--cenet and --action_dist beta exclude each other: {pinned}")
+        if self.algorithm_cfg.get("precision", "fp32") == "bf16":
+            raise ValueError(f"--cenet and --precision bf16 exclude each other: {pinned}")
+        if bool(self.cfg.get("exact_resume", False)):
+            raise NotImplementedError("--cenet with --exact_resume: CENet's state and its draws are not part of train_state_<it>.pt")
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("--cenet with a world size above 1 is not implemented: it trains in one process only")
+        check_layout(env)
+        targets = parse_targets(self.cfg.get("cenet_targets", "lin_vel"))
+        cols = target_columns(targets, env.num_obs)
+        if len(cols) > MAX_TARGETS:
+            raise ValueError(f"--cenet_targets: {len(cols)} columns, at most {MAX_TARGETS}")
+        out = {"targets": targets, "cols": cols, "latent_dim": int(self.cfg.get("cenet_latent_dim", 16)), "beta": float(self.cfg.get("cenet_beta", 1.0)),
+               "encoder_dims": check_dims(self.cfg.get("cenet_encoder_dims", (128, 64)), "cenet_encoder_dims"),
+               "decoder_dims": check_dims(self.cfg.get("cenet_decoder_dims", (64, 128)), "cenet_decoder_dims"),
+               "learning_rate": float(self.cfg.get("cenet_learning_rate", 1e-3)), "num_epochs": int(self.cfg.get("cenet_num_epochs", 1))}
+        check_values(out["latent_dim"], out["beta"], out["learning_rate"], out["num_epochs"])
+        return out
+
     def _check_noise(self):
         """what --noise_std_type log / --state_dependent_std do not combine with"""
         from .modules import NOISE_STD_TYPES
@@ -643,6 +711,8 @@ class OnPolicyRunner:
             raise ValueError("--action_dist beta and --rnd exclude each other: the combination is not pinned")
         if bool(self.cfg.get("estimator", False)):
             raise ValueError("--action_dist beta and --estimator exclude each other: the combination is not pinned")
+        if bool(self.cfg.get("cenet", False)):
+            raise ValueError("--action_dist beta and --cenet exclude each other: the combination is not pinned")
         if bool(self.policy_cfg.get("layer_norm", False)):
             raise ValueError("--action_dist beta and --layer_norm exclude each other: the combination is not pinned")
         if self.algorithm_cfg.get("precision", "fp32") != "fp32":
@@ -733,6 +803,9 @@ class OnPolicyRunner:
                 w.add_scalar("Train/rnd_weight", self.rnd.weight(it), it)
             if self.estimator is not None:
                 w.add_scalar("Loss/estimator", locs["mean_estimator_loss"], it)
+            if self.cenet is not None:
+                for name, value in zip(("estimation", "reconstruction", "kl"), locs["mean_cenet_losses"]):
+                    w.add_scalar("Loss/cenet_" + name, value, it)
             if self.multi_critic is not None:   # (Loss/value_function above is the sum over the heads)
                 spread = alg.multi_critic.stats[:, 1].tolist()   # the raw advantages' std per group, before normalisation
                 for k, name in enumerate(alg.multi_critic.groups.names):
@@ -801,6 +874,8 @@ class OnPolicyRunner:
             saved["rnd"] = self.rnd.checkpoint()
         if self.estimator is not None:   # (likewise): the network, its optimizer, the targets and hidden layers
             saved["estimator"] = self.estimator.checkpoint()
+        if self.cenet is not None:   # (likewise): encoder and decoder, their optimizer, the targets, the latent width and the hidden layers
+            saved["cenet"] = self.cenet.checkpoint()
         if self.value_norm is not None:   # (likewise): the mode, eps and the five statistics
             saved["value_norm"] = self.algorithm.value_norm.checkpoint()
         if self.layer_norm is not None:   # (likewise): that the hidden layers are Linear -> LayerNorm -> ELU, and the LayerNorms' eps
@@ -909,6 +984,15 @@ class OnPolicyRunner:
             raise ValueError(f"{path} was saved with estimator={theirs}, this runner has estimator={mine}: the policy's inputs would not be "
                              f"what it was trained on (pass {want}, or set train_cfg.runner.estimator / estimator_targets / "
                              "estimator_hidden_dims, to match the checkpoint)")
+        mine = dict(self.cenet.config) if self.cenet is not None else None
+        theirs = dict(loaded["cenet"]["config"]) if "cenet" in loaded else None
+        if theirs != mine:
+            want = ("--cenet --cenet_targets " + ",".join(theirs["targets"]) + f" --cenet_latent_dim {theirs['latent_dim']} --cenet_encoder_dims "
+                    + " ".join(str(h) for h in theirs["encoder_dims"]) + " --cenet_decoder_dims "
+                    + " ".join(str(h) for h in theirs["decoder_dims"])) if theirs is not None else "no --cenet"
+            raise ValueError(f"{path} was saved with cenet={theirs}, this runner has cenet={mine}: the policy's inputs would not be what it "
+                             f"was trained on (pass {want}, or set train_cfg.runner.cenet / cenet_targets / cenet_latent_dim / "
+                             "cenet_encoder_dims / cenet_decoder_dims, to match the checkpoint)")
         if not self.inference_only:   # (play.py and the exported policy use the actor only)
             theirs = loaded["value_norm"]["mode"] if "value_norm" in loaded else None
             if theirs != self.value_norm:
@@ -954,6 +1038,8 @@ class OnPolicyRunner:
             print(f"{path} holds an rnd entry, this runner has no --rnd: ignored")
         if self.estimator is not None:
             self.estimator.load_checkpoint(loaded["estimator"], load_optimizer)
+        if self.cenet is not None:
+            self.cenet.load_checkpoint(loaded["cenet"], load_optimizer)
         if self.value_norm is not None and "value_norm" in loaded and loaded["value_norm"]["mode"] == self.value_norm:
             self.algorithm.value_norm.load_checkpoint(loaded["value_norm"])
         self.current_learning_iteration = loaded["iter"]
@@ -1021,6 +1107,16 @@ class OnPolicyRunner:
             from .estimator import EstimatorPolicy
             self.estimator.net.eval()
             inner = EstimatorPolicy(self._mean_actor(), self.estimator.net)
+            if self.empirical_normalization:
+                self.obs_normalizer.eval()
+                inner = NormalizedPolicy(inner, self.obs_normalizer)
+            if self.obs_history_length > 1:
+                inner = HistoryPolicy(inner, self.env.num_obs, self.obs_history_length)
+            return inner.to(device if device is not None else self.device)
+        if self.cenet is not None:   # raw SINGLE frames in: history, the statistics as they are now, then [x | v_hat | mu] into the actor
+            from .cenet import CENetPolicy
+            self.cenet.encoder.eval()
+            inner = CENetPolicy(self._mean_actor(), self.cenet.encoder, self.cenet.num_outputs)
             if self.empirical_normalization:
                 self.obs_normalizer.eval()
                 inner = NormalizedPolicy(inner, self.obs_normalizer)

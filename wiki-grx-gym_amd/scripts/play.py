@@ -13,7 +13,8 @@ RECORD_FRAMES and MOVE_CAMERA are out of scope.  Files under `exporte
 
 A checkpoint trained with `--action_dist beta` needs the same flag here (and `--action_bounds` where the run had them): they
 reach the runner through `get_args` / `make_alg_runner`, whose `load` refuses a mismatch; the policy and the exported module then act on
-the Beta's mean in action units.
+the Beta's mean in action units.  A checkpoint trained with `--cenet` likewise needs `--cenet` and the run's `--cenet_targets`,
+`--cenet_latent_dim`, `--cenet_encoder_dims` and `--cenet_decoder_dims`; the policy and the exported module use z = mu.
 """
 import json
 import os
@@ -80,7 +81,8 @@ def play(args, steps=None, log_root="default"):
                                         normalizer=(ppo_runner.critic_obs_normalizer if privileged else ppo_runner.obs_normalizer)
                                         if ppo_runner.empirical_normalization else None,
                                         history=ppo_runner.critic_obs_history_length if privileged else ppo_runner.obs_history_length,
-                                        estimator=ppo_runner.estimator.net if getattr(ppo_runner, "estimator", None) is not None else None)
+                                        estimator=ppo_runner.estimator.net if getattr(ppo_runner, "estimator", None) is not None else None,
+                                        cenet=getattr(ppo_runner, "cenet", None))
         print(f"EXPORT_POLICY: Exported policy as jit script to: {exported}")
     os.makedirs(out_dir, exist_ok=True)
 

@@ -11,6 +11,7 @@
     python -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless --grad_penalty_coef 0.002              (a Lipschitz gradient penalty on the policy: DESIGN.md 4.17)
     python -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless --layer_norm                           (Linear -> LayerNorm -> ELU hidden layers: DESIGN.md 4.18)
     python -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless --reward_groups "track=cmd_diff_lin_vel_x,cmd_diff_lin_vel_y,cmd_diff_ang_vel_yaw;rest=*"   (a critic per reward group: DESIGN.md 4.19)
+    python -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless --cenet --cenet_latent_dim 16 --obs_history 5   (DreamWaQ's context-aided estimator: DESIGN.md 4.21)
     torchrun --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless
 """
 import os

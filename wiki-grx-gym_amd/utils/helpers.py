@@ -117,6 +117,21 @@ def get_args(argv=None):
     p.add_argument("--estimator_learning_rate", type=float, default=1e-3, help="Learning rate of --estimator's network (fixed; default 1e-3, not tuned)")
     p.add_argument("--estimator_num_epochs", type=int, default=1,
                    help="Passes of --estimator's regression over a rollout, in PPO's num_mini_batches minibatches (default 1, not tuned)")
+    p.add_argument("--cenet", action="store_true", default=False,
+                   help="A context-aided estimator network (DreamWaQ's CENet): an encoder regresses privileged quantities from the actor's input "
+                        "AND emits a stochastic latent from which a decoder predicts the next frame; [estimate | latent] is appended to the "
+                        "actor's input (saved in the checkpoint; play needs the same flag, targets, latent and hidden dims)")
+    p.add_argument("--cenet_targets", type=str, default="lin_vel",
+                   help="What --cenet's encoder regresses: --estimator_targets' names (default lin_vel, not tuned)")
+    p.add_argument("--cenet_latent_dim", type=int, default=16, help="Width of --cenet's latent z: 1..64 (default 16, not tuned)")
+    p.add_argument("--cenet_beta", type=float, default=1.0, help="Weight of --cenet's KL term (default 1.0, not tuned)")
+    p.add_argument("--cenet_encoder_dims", type=int, nargs="+", default=[128, 64],
+                   help="Hidden layers of --cenet's encoder: 1 to 3 widths of 1..1024 (default 128 64, not tuned)")
+    p.add_argument("--cenet_decoder_dims", type=int, nargs="+", default=[64, 128],
+                   help="Hidden layers of --cenet's decoder: 1 to 3 widths of 1..1024 (default 64 128, not tuned)")
+    p.add_argument("--cenet_learning_rate", type=float, default=1e-3, help="Learning rate of --cenet's networks (fixed; default 1e-3, not tuned)")
+    p.add_argument("--cenet_num_epochs", type=int, default=1,
+                   help="Passes of --cenet's update over a rollout, in PPO's num_mini_batches minibatches (default 1, not tuned)")
     p.add_argument("--noise_std_type", type=str, choices=["scalar", "log"],
                    help="The action noise's parameter: std itself (scalar, default) or log_std with sigma = exp(log_std), which cannot reach "
                         "zero (saved in the checkpoint; play needs the same value)")
@@ -217,6 +232,16 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
             r.estimator_hidden_dims = [int(h) for h in getattr(args, "estimator_hidden_dims", [128, 64])]
             r.estimator_learning_rate = float(getattr(args, "estimator_learning_rate", 1e-3))
             r.estimator_num_epochs = int(getattr(args, "estimator_num_epochs", 1))
+        if getattr(args, "cenet", False):   # (likewise; the --cenet_* values travel only with --cenet)
+            r = cfg_train.runner
+            r.cenet = True
+            r.cenet_targets = getattr(args, "cenet_targets", "lin_vel")
+            r.cenet_latent_dim = int(getattr(args, "cenet_latent_dim", 16))
+            r.cenet_beta = float(getattr(args, "cenet_beta", 1.0))
+            r.cenet_encoder_dims = [int(h) for h in getattr(args, "cenet_encoder_dims", [128, 64])]
+            r.cenet_decoder_dims = [int(h) for h in getattr(args, "cenet_decoder_dims", [64, 128])]
+            r.cenet_learning_rate = float(getattr(args, "cenet_learning_rate", 1e-3))
+            r.cenet_num_epochs = int(getattr(args, "cenet_num_epochs", 1))
         if getattr(args, "recurrent", False):   # (likewise: the policy config has no rnn_hidden_size otherwise)
             cfg_train.runner.policy_class_name = "ActorCriticRecurrent"
             cfg_train.policy.rnn_hidden_size = int(getattr(args, "rnn_hidden_size", 256))
@@ -267,7 +292,7 @@ def get_load_path(root, load_run=-1, checkpoint=-1):
     return os.path.join(load_run, model)
 
 
-def export_policy_as_jit(actor_critic, path, normalizer=None, history=1, estimator=None):
+def export_policy_as_jit(actor_critic, path, normalizer=None, history=1, estimator=None, cenet=None):
     """A recurrent actor_critic (rl.recurrent.ActorCriticRecurrent): the exported module is an nn.LSTM with its state in buffers in front
     of the actor's layers (rl.recurrent.ExportedRecurrentPolicy: one raw frame per call, `reset_memory()` and `reset(dones)` exported).
     `normalizer` (an rl.normalizer.EmpiricalNormalization): the exported module takes RAW observations and normalises them itself.
@@ -277,7 +302,8 @@ def export_policy_as_jit(actor_critic, path, normalizer=None, history=1, estimat
     An actor_critic with `action_dist="beta"`: the exported module returns the Beta's mean in action units, lo + span * alpha / (alpha + beta),
     with lo / span as its own buffers (rl.beta.BetaMeanHead).
     `estimator` (the network of an rl.estimator.StateEstimator): behind history and normaliser the module appends the estimate to the
-    actor's input itself (rl.estimator.EstimatorPolicy); a consumer still feeds raw single frames"""
+    actor's input itself (rl.estimator.EstimatorPolicy); a consumer still feeds raw single frames.
+    `cenet` (an rl.cenet.CENet): likewise with [v_hat | mu] of its encoder, z = mu (rl.cenet.CENetPolicy); the decoder is not exported"""
     os.makedirs(path, exist_ok=True)
     path = os.path.join(path, "policy_jit.pt")
     if getattr(actor_critic, "is_recurrent", False):
@@ -292,6 +318,10 @@ def export_policy_as_jit(actor_critic, path, normalizer=None, history=1, estimat
         from ..rl.estimator import EstimatorPolicy
         model = EstimatorPolicy(model, copy.deepcopy(estimator).to("cpu"))
         appended = estimator.output_size
+    if cenet is not None:
+        from ..rl.cenet import CENetPolicy
+        model = CENetPolicy(model, copy.deepcopy(cenet.encoder).to("cpu"), cenet.num_outputs)
+        appended = cenet.num_outputs
     if normalizer is not None:
         from ..rl.normalizer import NormalizedPolicy
         model = NormalizedPolicy(model, copy.deepcopy(normalizer).to("cpu"))
