@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from tests import ppo_ref
+from tests.mlp_layer_ref import layer_bound
 from tests.ppo_ref import U32
 from wiki_grx_gym_amd.rl import fused_loss as fl
 from wiki_grx_gym_amd.rl.modules import ActorCriticMLP
@@ -291,9 +292,7 @@ def _head(lib, X, W, bias, std, eps):
 
 def _check_head(got, X, W, bias, std, eps, tag):
     ref = ppo_ref.policy_head_ref(X, W, bias, std, eps)
-    K = X.shape[1]
-    absprod = X.double().abs() @ W.double().abs().t() + (bias.double().abs() if bias is not None else 0.0)
-    tol_mu = (K + 2) * U32 * absprod + 1e-30   # a k-ordered fp32 chain of K multiply-adds plus the bias
+    tol_mu = layer_bound(X, W, bias) + 1e-30   # a k-ordered fp32 chain of K multiply-adds plus the bias: (K + 2) U32 (|X| |W|^T + |bias|)
     e = (got["mu"].double() - ref["mu"]).abs()
     assert bool((e <= tol_mu).all()), (tag, "mu", float((e / tol_mu).max()))
     sd, ep = std.double(), eps.double()
@@ -334,6 +333,26 @@ def test_policy_head_matches_float64(A):
                 Xm.copy_(X)
                 assert Xm.data_ptr() % 16 == 4
                 _check_head(_head(lib, Xm, W, bias, std, eps), X, W, bias, std, eps, (A, K, M, "misaligned"))
+
+
+@pytest.mark.parametrize("A", [1, 10, 31, 32])
+def test_policy_head_mu_is_the_layer_kernels_bits(A):
+    """grx_mlp_policy_head's mu is grx_mlp_layer(X, W, bias, elu = 0) bit for bit (the same kernel body with another epilogue), with and
+    without a bias: one K chunk of one k, two full chunks, two chunks plus one MFMA (scalar loads); one row and a second, one-row tile.
+    tests/test_noise_std_gpu.py holds the state-dependent head to the same; tests/test_mlp_layer_gpu.py holds the layer kernel itself."""
+    lib = fl.load_ppo_library()
+    for K in (1, 128, 130):
+        for M in (1, 65):
+            g = _gen(7 + A * 100000 + K * 1000 + M)
+            X = torch.randn(M, K, device=DEV, generator=g)
+            W = torch.randn(A, K, device=DEV, generator=g) / math.sqrt(K)
+            W[:, 0] += torch.arange(A, device=DEV) * 0.01
+            std = torch.linspace(0.05, 1.0, A, device=DEV)
+            eps = torch.randn(M, A, device=DEV, generator=g)
+            for bias in (torch.randn(A, device=DEV, generator=g) * 0.1, None):
+                mu = _head(lib, X, W, bias, std, eps)["mu"]
+                y = fl._layer(lib, X, W, bias, False, _stream())
+                assert torch.equal(mu.view(torch.int32), y.view(torch.int32)), (A, K, M, bias is not None, float((mu - y).abs().max()))
 
 
 # ---- grx_ppo_step_tail ----------------------------------------------------------------------------------------------------------
