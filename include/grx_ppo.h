@@ -301,4 +301,7 @@ int grx_rnd_reward(int N, int E, const float* pred, const float* targ, float gam
 /* ... and the context-aided estimator network: the rollout's head behind the encoder, the reparameterisation with its
  * backward, and the estimation + reconstruction + KL loss, csrc/grx_ppo_cenet.hip in the same library */
 #include "grx_ppo_cenet.h"
+/* ... and constraints as terminations: the per-step violations, running maxima and termination probabilities with the
+ * reward row's edit, and the GAE pass that discounts by them, csrc/grx_ppo_cat.hip in the same library */
+#include "grx_ppo_cat.h"
 #endif

@@ -69,7 +69,8 @@ class PPO:
                  weight_decay=0.0, max_grad_norm=1.0, use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01,
                  device="cpu", storage_class="RolloutStorage", precision="fp32", symmetry=None, symmetry_coef=1.0, symmetry_maps=None,
                  smooth=None, smooth_temporal_coef=0.1, smooth_spatial_coef=0.1, smooth_sigma=0.05, value_norm=None, value_norm_eps=1e-5,
-                 grad_penalty_coef=None, reward_groups=None, reward_group_weights=None, **kwargs):
+                 grad_penalty_coef=None, reward_groups=None, reward_group_weights=None, constraints=None, constraint_tau=0.95,
+                 constraint_ramp_its=1000, constraint_reward_clip="zero", **kwargs):
         if kwargs:
             print("PPO.__init__ got unexpected arguments, which will be ignored: " + str(list(kwargs)))
         # precision="bf16": every hidden layer of actor and critic multiplies bf16 operands into fp32 accumulators -- in the rollout's
@@ -196,6 +197,12 @@ class PPO:
         self.multi_critic = None
         if reward_groups is not None:
             self._init_multi_critic(reward_groups, reward_group_weights)
+        # constraints as terminations (rl/constraints.py): a constraint violation becomes a termination probability per
+        # (step, env) that scales the stored reward and the discount inside GAE; the update is untouched.  Not a config key: `--constraints`
+        # / `--constraint_*` or assignments to train_cfg.algorithm set it; None imports nothing of it
+        self.constraints = None
+        if constraints is not None:
+            self._init_constraints(constraints, constraint_tau, constraint_ramp_its, constraint_reward_clip)
         self.num_updates = 0
         self._params = [p for p in self.actor_critic.parameters() if p.requires_grad]
         n = sum(p.numel() for p in self._params)
@@ -359,6 +366,33 @@ class PPO:
             print("PPO: GRX_MC_FUSED=0 -> the minibatch step runs eagerly (GRX_PPO_GRAPH=0)")
             self._use_graph = self._two_streams = False
 
+    def _init_constraints(self, spec, tau, ramp_its, reward_clip):
+        why = "the combination is not pinned"
+        if self._recurrent:
+            raise ValueError(f"PPO: --constraints and --recurrent exclude each other: {why}")
+        if self.value_norm is not None:
+            raise ValueError("PPO: --constraints and --value_norm exclude each other: both replace compute_returns")
+        if self.multi_critic is not None:
+            raise ValueError("PPO: --constraints and --reward_groups exclude each other: both replace compute_returns")
+        if self.symmetry is not None:
+            raise ValueError(f"PPO: --constraints and --symmetry exclude each other: {why}")
+        if self.smooth is not None:
+            raise ValueError(f"PPO: --constraints and --smooth exclude each other: {why}")
+        if self.grad_penalty_coef is not None:
+            raise ValueError(f"PPO: --constraints and --grad_penalty_coef exclude each other: {why}")
+        if self._state_dependent:
+            raise ValueError(f"PPO: --constraints and --state_dependent_std exclude each other: {why}")
+        if self._layer_norm:
+            raise ValueError(f"PPO: --constraints and --layer_norm exclude each other: {why}")
+        if self._beta:
+            raise ValueError(f"PPO: --constraints and --action_dist beta exclude each other: {why}")
+        if self.precision == "bf16":
+            raise ValueError(f"PPO: --constraints and --precision bf16 exclude each other: {why}")
+        if _world() > 1:
+            raise NotImplementedError("PPO: --constraints with a world size above 1 is not implemented: the column maxima are per process")
+        from .constraints import Constraints
+        self.constraints = Constraints(spec, tau, ramp_its, reward_clip, self.device)
+
     def _init_smooth(self, smooth, coef_t, coef_s, sigma):
         from .smooth import blocks, check_values
         succ, pert = blocks(smooth)
@@ -392,6 +426,8 @@ class PPO:
                                       [ac.num_actor_output], self.device)
         if self.multi_critic is not None:   # (the K-wide values / rewards / returns beside it)
             self.multi_critic.init_storage(num_envs, num_transitions_per_env)
+        if self.constraints is not None:   # (the [T, N] termination probabilities beside it)
+            self.constraints.init_storage(num_envs, num_transitions_per_env)
 
     def test_mode(self):
         self.actor_critic.eval()
@@ -561,7 +597,14 @@ class PPO:
         storage's reward row of that step in place (the row holds the env's reward and the time-out bootstrap by then)"""
         if self.multi_critic is not None:   # (the runner refuses the pair before it builds anything; a caller that assigns `rnd` itself ends here)
             raise ValueError("PPO: --reward_groups and --rnd exclude each other: the intrinsic reward belongs to no group")
+        if self.constraints is not None:   # (likewise)
+            raise ValueError("PPO: --constraints and --rnd exclude each other: the order of the two edits of the reward row is not pinned")
         self.rnd.rollout_step(frame, self.storage.rewards[step], step)
+
+    def constraint_step(self, step):
+        """after process_env_step of rollout step `step`: the step's termination probabilities from the env's tensors as they are now, and
+        the storage's reward row of that step scaled by (1 - delta) in place (the row holds the env's reward and the time-out bootstrap by then)"""
+        self.constraints.step(step, self.storage)
 
     def compute_returns(self, last_critic_obs):
         self._join_critic()
@@ -576,6 +619,9 @@ class PPO:
             return
         if self.multi_critic is not None:   # GAE and the advantage normalisation per group, the advantages their weighted sum
             self.multi_critic.compute_returns(self.storage, last_values, self.gamma, self.lam)
+            return
+        if self.constraints is not None:   # the storage's loop with alive = (1 - done)(1 - delta), the advantages normalised as ever
+            self.constraints.compute_returns(self.storage, last_values, self.gamma, self.lam)
             return
         self.storage.compute_returns(last_values, self.gamma, self.lam)
 

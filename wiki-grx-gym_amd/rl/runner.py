@@ -151,6 +151,14 @@ class OnPolicyRunner:
             self._check_multi_critic(env)
         else:
             self.algorithm_cfg = {k: v for k, v in self.algorithm_cfg.items() if k not in ("reward_groups", "reward_group_weights")}
+        # constraints as terminations: constraint violations become termination probabilities that scale the rollout's
+        # rewards and the discount inside GAE.  Not config keys either (`--constraints` / `--constraint_*` or assignments to
+        # train_cfg.algorithm set them): without `constraints` nothing of rl/constraints.py is imported
+        self.constraints = None   # the "constraints" entry of a checkpoint of this run, without the state: only under the flag
+        if self.algorithm_cfg.get("constraints") is not None:   # (an empty spec is refused by the parser, not taken for "no flag")
+            self._check_constraints()
+        else:
+            self.algorithm_cfg = {k: v for k, v in self.algorithm_cfg.items() if k != "constraints" and not k.startswith("constraint_")}
         self.estimator = None
         estimator_cfg = self._check_estimator(env) if bool(self.cfg.get("estimator", False)) else None
         # a context-aided estimator network: the estimator's regression plus a stochastic latent that a decoder predicts the
@@ -202,6 +210,8 @@ class OnPolicyRunner:
             if self.multi_critic is not None:   # the step kernel's per-term tables, zero-copy views the rollout's store reads every step
                 base = env._sim.tensor("BASE_REWARD_TERMS") if self.algorithm.multi_critic.groups.uses_base else None
                 self.algorithm.multi_critic.bind_tables(env._sim.tensor("REWARD_TERMS"), base)
+            if self.constraints is not None:   # the env's tensors and limits, zero-copy views the rollout's step pass reads every step
+                self.algorithm.constraints.bind(env)
             if rnd_cfg is not None:   # (after the policy: its initial parameters are those of a run without the flag)
                 from .rnd import RandomNetworkDistillation
                 state = rnd_cfg.get("state", "privileged")
@@ -310,6 +320,8 @@ class OnPolicyRunner:
             start = time.time()
             if self.rnd is not None:
                 self.rnd.iteration = it
+            if self.constraints is not None:   # this iteration's maximum termination probabilities (a resumed run continues the ramp)
+                alg.constraints.set_iteration(it)
             with torch.inference_mode():
                 if self.estimator is not None:   # the row this rollout starts with was built from the frames parked last
                     self.estimator.begin_rollout()
@@ -342,6 +354,8 @@ class OnPolicyRunner:
                         alg.process_env_step(rewards, dones, infos)
                     if self.rnd is not None:   # into the storage's reward row of this step; the logged episode rewards stay the env's
                         alg.rnd_step(rnd_frame, t_)
+                    if self.constraints is not None:   # likewise: delta from the env's tensors as the step left them, the row scaled by 1 - delta
+                        alg.constraint_step(t_)
                 if self.log_dir is not None:   # one device->host transfer per iteration
                     m = alg.storage.dones.squeeze(-1).bool()
                     rewbuffer.extend(done_rew[m].cpu().tolist())
@@ -565,6 +579,49 @@ class OnPolicyRunner:
         self.algorithm_cfg = {**self.algorithm_cfg, "reward_groups": groups, "reward_group_weights": weights}
         self.policy_cfg = {**self.policy_cfg, "num_critic_outputs": groups.K}
         self.multi_critic = groups.entry(weights)
+
+    def _check_constraints(self):
+        """what --constraints does not combine with; parses the spec and checks its options, so that PPO gets what it will keep"""
+        from .constraints import check_options, parse_constraints
+        why = "the combination is not pinned"
+        if self.recurrent:
+            raise ValueError(f"--constraints and --recurrent exclude each other: {why}")
+        if self.value_norm is not None:
+            raise ValueError("--constraints and --value_norm exclude each other: both replace compute_returns")
+        if self.multi_critic is not None:
+            raise ValueError("--constraints and --reward_groups exclude each other: both replace compute_returns")
+        if self._rnd_requested:
+            raise ValueError("--constraints and --rnd exclude each other: the order of the two edits of the reward row is not pinned")
+        if self.distill_from is not None:
+            raise ValueError("--constraints and --distill_from exclude each other: a distillation run has no returns to discount")
+        if self.action_dist is not None:
+            raise ValueError(f"--constraints and --action_dist beta exclude each other: {why}")
+        if self.symmetry is not None:
+            raise ValueError(f"--constraints and --symmetry exclude each other: {why}")
+        if self.smooth is not None:
+            raise ValueError(f"--constraints and --smooth exclude each other: {why}")
+        if self.grad_penalty_coef is not None:
+            raise ValueError(f"--constraints and --grad_penalty_coef exclude each other: {why}")
+        if self.state_dependent_std:
+            raise ValueError(f"--constraints and --state_dependent_std exclude each other: {why}")
+        if self.layer_norm is not None:
+            raise ValueError(f"--constraints and --layer_norm exclude each other: {why}")
+        if bool(self.cfg.get("estimator", False)):
+            raise ValueError(f"--constraints and --estimator exclude each other: {why}")
+        if bool(self.cfg.get("cenet", False)):
+            raise ValueError(f"--constraints and --cenet exclude each other: {why}")
+        if self.algorithm_cfg.get("precision", "fp32") == "bf16":
+            raise ValueError(f"--constraints and --precision bf16 exclude each other: {why}")
+        if bool(self.cfg.get("exact_resume", False)):
+            raise NotImplementedError("--constraints with --exact_resume is not implemented: c_max and the previous actions are not part of "
+                                      "train_state_<it>.pt")
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("--constraints with a world size above 1 is not implemented: the column maxima are per process")
+        a = self.algorithm_cfg
+        spec = parse_constraints(a["constraints"])
+        tau, ramp, clip = check_options(a.get("constraint_tau", 0.95), a.get("constraint_ramp_its", 1000), a.get("constraint_reward_clip", "zero"))
+        self.algorithm_cfg = {**a, "constraints": spec, "constraint_tau": tau, "constraint_ramp_its": ramp, "constraint_reward_clip": clip}
+        self.constraints = {"spec": spec.key(), "tau": tau, "ramp_its": ramp, "reward_clip": clip}
 
     def _check_value_norm(self):
         """what --value_norm does not combine with"""
@@ -811,6 +868,9 @@ class OnPolicyRunner:
                 for k, name in enumerate(alg.multi_critic.groups.names):
                     w.add_scalar("Loss/value_function_" + name, alg.multi_critic.mean_head_losses[k], it)
                     w.add_scalar("Train/adv_std_" + name, spread[k], it)
+            if self.constraints is not None:   # of the rollout just trained on: one read-back
+                for name, value in alg.constraints.scalars().items():
+                    w.add_scalar("Constraint/" + name, value, it)
             if self.value_norm is not None:   # (Loss/value_function above is in normalised units then)
                 w.add_scalar("Train/value_norm_mean", alg.value_norm.mean.item(), it)
                 w.add_scalar("Train/value_norm_std", alg.value_norm.std.item(), it)
@@ -883,6 +943,8 @@ class OnPolicyRunner:
         if self.multi_critic is not None:   # (likewise): the groups' names and terms, the weights
             saved["multi_critic"] = {"groups": {n: list(t) for n, t in self.multi_critic["groups"].items()},
                                      "weights": list(self.multi_critic["weights"])}
+        if self.constraints is not None:   # (likewise): the spec, tau, the ramp, the clip and the running column maxima
+            saved["constraints"] = self.algorithm.constraints.checkpoint()
         torch.save(saved, path)
         if self.exact_resume:
             torch.save(self._train_state(), train_state_path(path))
@@ -1007,6 +1069,17 @@ class OnPolicyRunner:
                 raise ValueError(f"{path} was saved with multi_critic={theirs}, this runner has multi_critic={self.multi_critic}: the critic's "
                                  f"heads would not be the ones that were trained (pass {want}, or set train_cfg.algorithm.reward_groups / "
                                  "reward_group_weights, to match the checkpoint)")
+            theirs = loaded.get("constraints")
+            if (None if theirs is None else theirs["spec"]) != (None if self.constraints is None else self.constraints["spec"]):
+                if theirs is not None:
+                    from .constraints import ConstraintSpec
+                    want = f"--constraints \"{ConstraintSpec(theirs['spec']).text()}\""
+                else:
+                    want = "no --constraints"
+                raise ValueError(f"{path} was saved with constraints={None if theirs is None else theirs['spec']}, this runner has constraints="
+                                 f"{None if self.constraints is None else self.constraints['spec']}: the running column maxima would not be "
+                                 f"the spec's (pass {want}, or set train_cfg.algorithm.constraints, to match the checkpoint; the flag is "
+                                 "--constraints)")
         elif _groups_key(loaded.get("multi_critic")) != _groups_key(self.multi_critic):   # (the actor alone is used: the critic and the optimizer stay what they are)
             mine = self.algorithm.actor_critic.state_dict()
             loaded["model_state_dict"] = {k: (mine[k] if k.startswith("critic.") else v) for k, v in loaded["model_state_dict"].items()}
@@ -1040,6 +1113,8 @@ class OnPolicyRunner:
             self.estimator.load_checkpoint(loaded["estimator"], load_optimizer)
         if self.cenet is not None:
             self.cenet.load_checkpoint(loaded["cenet"], load_optimizer)
+        if self.constraints is not None and not self.inference_only:   # (c_max; the previous actions restart at zero)
+            self.algorithm.constraints.load_checkpoint(loaded["constraints"])
         if self.value_norm is not None and "value_norm" in loaded and loaded["value_norm"]["mode"] == self.value_norm:
             self.algorithm.value_norm.load_checkpoint(loaded["value_norm"])
         self.current_learning_iteration = loaded["iter"]

@@ -12,6 +12,7 @@
     python -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless --layer_norm                           (Linear -> LayerNorm -> ELU hidden layers: DESIGN.md 4.18)
     python -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless --reward_groups "track=cmd_diff_lin_vel_x,cmd_diff_lin_vel_y,cmd_diff_ang_vel_yaw;rest=*"   (a critic per reward group: DESIGN.md 4.19)
     python -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless --cenet --cenet_latent_dim 16 --obs_history 5   (DreamWaQ's context-aided estimator: DESIGN.md 4.21)
+    python -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless --constraints "torque:0.05..0.25,dof_pos:0.25,action_rate:0.25@1.5,upright:1.0@0.7"   (constraints as terminations: DESIGN.md 4.22)
     torchrun --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 -m wiki_grx_gym_amd.scripts.train --task GR1T1 --headless
 """
 import os

@@ -147,6 +147,18 @@ def get_args(argv=None):
                         "normalisation run per group.  Saved in the checkpoint; --resume needs the same spec")
     p.add_argument("--reward_group_weights", type=str,
                    help="Weights `w1,...,wK` of --reward_groups' normalised group advantages in their sum (default all 1.0, not tuned)")
+    p.add_argument("--constraints", type=str,
+                   help="Constraints as terminations (CaT): `family:p[@L],...` with the families torque, dof_vel, dof_pos, action_rate@L, "
+                        "upright@L; p is the family's maximum termination probability, one number in [0, 1] or `p_lo..p_hi` ramped over "
+                        "--constraint_ramp_its iterations.  A violation scales the reward and the discount inside GAE.  Saved in the "
+                        "checkpoint; --resume needs the same spec")
+    p.add_argument("--constraint_tau", type=float, default=0.95,
+                   help="Decay of --constraints' running column maxima, in [0, 1) (default 0.95, the paper's)")
+    p.add_argument("--constraint_ramp_its", type=int, default=1000,
+                   help="Iterations over which --constraints' `p_lo..p_hi` probabilities ramp, >= 1 (default 1000, not tuned)")
+    p.add_argument("--constraint_reward_clip", type=str, choices=["zero", "none"], default="zero",
+                   help="Under --constraints the stored reward is (1 - delta) max(r, 0) (zero, default: ending early never pays) or "
+                        "(1 - delta) r (none)")
     p.add_argument("--action_dist", type=str, choices=["gaussian", "beta"],
                    help="The policy's action distribution: a Gaussian (default) or a Beta on the env's action box "
                         "(normalization.clip_actions_min / clip_actions_max), which cannot sample outside it.  Saved in the checkpoint; "
@@ -255,6 +267,12 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
             cfg_train.algorithm.reward_groups = args.reward_groups
             if getattr(args, "reward_group_weights", None) is not None:
                 cfg_train.algorithm.reward_group_weights = args.reward_group_weights
+        if getattr(args, "constraints", None) is not None:   # (likewise; the --constraint_* values travel only with --constraints)
+            a = cfg_train.algorithm
+            a.constraints = args.constraints
+            a.constraint_tau = float(getattr(args, "constraint_tau", 0.95))
+            a.constraint_ramp_its = int(getattr(args, "constraint_ramp_its", 1000))
+            a.constraint_reward_clip = getattr(args, "constraint_reward_clip", "zero")
         if getattr(args, "action_dist", None) is not None:   # (likewise: the policy config has no such keys otherwise)
             cfg_train.policy.action_dist = args.action_dist
         if getattr(args, "action_bounds", None) is not None:   # (likewise)
