@@ -304,4 +304,7 @@ int grx_rnd_reward(int N, int E, const float* pred, const float* targ, float gam
 /* ... and constraints as terminations: the per-step violations, running maxima and termination probabilities with the
  * reward row's edit, and the GAE pass that discounts by them, csrc/grx_ppo_cat.hip in the same library */
 #include "grx_ppo_cat.h"
+/* ... and the recurrent distillation student: one step of the LSTM's backward through time -- dG_next W_hh, the sum with
+ * the loss's gradient and the cell's element-wise backward -- in one launch, csrc/grx_ppo_bptt.hip in the same library */
+#include "grx_ppo_bptt.h"
 #endif

@@ -12,7 +12,13 @@ own (usually privileged) stream -- DAgger.
 The loss (with its gradient) and the per-step store are one HIP entry point each (include/grx_ppo.h grx_distill_loss /
 grx_distill_store) for contiguous fp32 tensors on a HIP device; their torch spellings below serve CPU tensors and strided input, and
 GRX_DISTILL_FUSED=0 forces them on the device too.  Nothing here is captured in a HIP graph: the step runs eagerly, without host
-synchronisation inside the minibatch loop (the mean behaviour loss is read back once per update)."""
+synchronisation inside the minibatch loop (the mean behaviour loss is read back once per update).
+
+A recurrent student (`--student_recurrent`, StudentTeacherRecurrent) has an LSTM over single frames in front of its MLP:
+    act():      at the rollout's step 0 the memory's state goes to the storage (h0, c0); one cell launch, then the MLP on h
+    update():   truncated back-propagation through time -- windows of `gradient_length` steps over contiguous env ranges, the state
+                carried from window to window as data, one optimizer step per (range, window); the backward's per-step chain is one
+                launch (rl.recurrent.LSTMSequenceBPTT, include/grx_ppo_bptt.h grx_lstm_bptt_step)"""
 import contextlib
 import ctypes as C
 import os
@@ -233,6 +239,65 @@ class StudentTeacher(nn.Module):
             return self.teacher(teacher_observations)
 
 
+class StudentTeacherRecurrent(StudentTeacher):
+    """`--student_recurrent` (rsl_rl 2.x `StudentTeacherRecurrent` with an MLP teacher): the student is `memory_a`, one LSTM
+    layer of hidden size H over single actor frames, in front of `actor`, an MLP of input width H -- the attribute names
+    rl.recurrent.RecurrentPolicy and ExportedRecurrentPolicy read.  The teacher stays the frozen MLP on its own stream.
+    State dict: memory_a.rnn.*, actor.*, std, teacher.*"""
+    is_recurrent = True
+
+    def __init__(self, student_num_input, teacher_num_input, num_actions, actor_hidden_dims=(256, 256, 256), teacher_hidden_dims=(256, 256, 256),
+                 activation="elu", noise_std=0.1, rnn_hidden_size=256, **_):
+        from .recurrent import Memory, _MemoryMLP, check_rnn
+        H = check_rnn("lstm", 1, rnn_hidden_size)   # (the refusal, before anything is built)
+        nn.Module.__init__(self)
+        self.num_actor_input, self.num_actor_output, self.num_teacher_input = int(student_num_input), int(num_actions), int(teacher_num_input)
+        self.rnn_hidden_size = H
+        self.memory_a = Memory(student_num_input, H)
+        self.actor = _MemoryMLP(H, num_actions, actor_hidden_dims, activation)
+        self.teacher = MLP(teacher_num_input, num_actions, teacher_hidden_dims, activation)
+        for p in self.teacher.parameters():
+            p.requires_grad_(False)
+        self.teacher.eval()
+        self.register_buffer("std", float(noise_std) * torch.ones(num_actions))
+
+    def student_parameters(self):
+        return list(self.memory_a.parameters()) + list(self.actor.parameters())
+
+    def reset(self, dones=None):
+        self.memory_a.reset(dones)
+
+    def act(self, observations, **_):
+        mean = self.actor(self.memory_a.step(observations))
+        return mean + self.std * torch.randn_like(mean)
+
+    def act_inference(self, observations):
+        return self.actor(self.memory_a.step(observations))
+
+
+class RecurrentDistillStorage(DistillStorage):
+    """DistillStorage plus the state the student's memory had before the rollout's first step, [N, H] each, and the update's env ranges
+    (rl.recurrent.RecurrentRolloutStorage.env_ranges' rule: contiguous, in order, the tail dropped)"""
+
+    def __init__(self, num_envs, num_transitions_per_env, obs_dim, num_actions, hidden_size, device):
+        super().__init__(num_envs, num_transitions_per_env, obs_dim, num_actions, device)
+        self.h0 = torch.zeros(self.num_envs, int(hidden_size), device=device)
+        self.c0 = torch.zeros(self.num_envs, int(hidden_size), device=device)
+
+    def set_start_state(self, state):
+        self.h0.copy_(state[0]); self.c0.copy_(state[1])
+
+    def env_ranges(self, num_mini_batches):
+        from .recurrent import RecurrentRolloutStorage
+        return RecurrentRolloutStorage.env_ranges(self, num_mini_batches)
+
+    def windows(self, gradient_length):
+        """[t0, t1) of every truncated-BPTT window: gradient_length steps each, the last one maybe shorter; 0: the whole rollout"""
+        T = self.num_transitions_per_env
+        L = T if gradient_length == 0 else min(int(gradient_length), T)
+        return [(t0, min(t0 + L, T)) for t0 in range(0, T, L)]
+
+
 class _Transition:
     def __init__(self):
         self.clear()
@@ -250,7 +315,7 @@ class Distillation:
     optimizer), PPO's keyword arguments accepted and -- where distillation has no use for them -- ignored."""
 
     def __init__(self, actor_critic=None, num_learning_epochs=1, num_mini_batches=1, learning_rate=1e-3, max_grad_norm=1.0, weight_decay=0.0,
-                 device="cpu", loss_type="mse", precision="fp32", **_):
+                 device="cpu", loss_type="mse", precision="fp32", gradient_length=15, **_):
         if precision != "fp32":
             raise ValueError(f"Distillation: precision={precision!r} is not available, the student trains in fp32")
         if loss_type not in LOSSES:
@@ -265,7 +330,12 @@ class Distillation:
         self.storage, self.transition = None, _Transition()
         self._on_device = torch.device(device).type == "cuda"
         self._fused = self._on_device and _fused_enabled()         # the two grx_distill_* entry points
-        self._params = [p for p in self.actor_critic.actor.parameters()]
+        # a recurrent student (StudentTeacherRecurrent): the memory's parameters train too, the update is truncated BPTT
+        self._recurrent = bool(getattr(self.actor_critic, "is_recurrent", False))
+        self.gradient_length = int(gradient_length)
+        if self._recurrent and self.gradient_length < 0:
+            raise ValueError(f"Distillation: distill_gradient_length must be an integer >= 0 (0: the whole rollout), not {gradient_length!r}")
+        self._params = self.actor_critic.student_parameters() if self._recurrent else [p for p in self.actor_critic.actor.parameters()]
         if self._on_device:
             # PPO's device-resident optimizer: the learning rate is a device scalar, the NaN-skip needs no host round trip
             self._lr_t = torch.tensor(self.learning_rate, device=device)
@@ -281,6 +351,10 @@ class Distillation:
     # ---- the rollout -----------------------------------------------------------------------------------------------------------------
     def init_storage(self, num_envs, num_transitions_per_env, **_):
         ac = self.actor_critic
+        if self._recurrent:
+            self.storage = RecurrentDistillStorage(num_envs, num_transitions_per_env, ac.num_actor_input, ac.num_actor_output, ac.rnn_hidden_size,
+                                                   self.device)
+            return
         self.storage = DistillStorage(num_envs, num_transitions_per_env, ac.num_actor_input, ac.num_actor_output, self.device)
 
     def test_mode(self):
@@ -291,6 +365,8 @@ class Distillation:
 
     def act(self, observations, teacher_observations):
         ac, t = self.actor_critic, self.transition
+        if self._recurrent:
+            return self._act_recurrent(observations, teacher_observations)
         with torch.no_grad():
             if (self._on_device and ac.num_actor_output <= 32 and mlp_can_fuse(ac.actor, observations)
                     and mlp_can_fuse(ac.teacher, teacher_observations)):
@@ -300,6 +376,25 @@ class Distillation:
                 t.labels = mlp_forward(ac.teacher, teacher_observations)
             else:
                 t.actions = ac.act(observations).detach()
+                t.labels = ac.evaluate(teacher_observations).detach()
+        t.observations = observations
+        return t.actions
+
+    def _act_recurrent(self, observations, teacher_observations):
+        """a recurrent student's step: the memory's state before the rollout's first step goes to the storage, then one cell launch, the
+        student's MLP and the sampling on h, the teacher's label on its own stream"""
+        ac, t, st = self.actor_critic, self.transition, self.storage
+        with torch.no_grad():
+            if st.step == 0:
+                st.set_start_state(ac.memory_a.start_state(observations.shape[0], observations.device))
+            h = ac.memory_a.step(observations)
+            if (self._on_device and ac.num_actor_output <= 32 and ac.actor.fusable(h) and mlp_can_fuse(ac.teacher, teacher_observations)):
+                eps = torch.randn(h.shape[0], ac.num_actor_output, device=h.device)
+                t.actions = policy_act(ac.actor, ac.std, h, eps)[0]
+                t.labels = mlp_forward(ac.teacher, teacher_observations)
+            else:
+                mean = ac.actor(h)
+                t.actions = (mean + ac.std * torch.randn_like(mean)).detach()
                 t.labels = ac.evaluate(teacher_observations).detach()
         t.observations = observations
         return t.actions
@@ -344,9 +439,54 @@ class Distillation:
         self.optimizer.zero_grad(set_to_none=False)
         return loss
 
-    def update(self):
+    def window_batches(self):
+        """what a recurrent student's update walks, in order: per env range (a, b) its start state (h0, c0)[a:b] and, per window [t0, t1),
+        (observations [t1 - t0, b - a, D], resets [t1 - t0, b - a] uint8, labels [(t1 - t0)(b - a), A]).  resets[t] = dones[t - 1]: a step
+        starts from zero where the step before ended an episode; none at the rollout's step 0 (h0 / c0 hold that reset already)"""
         st = self.storage
-        mb = st.num_envs * st.num_transitions_per_env // self.num_mini_batches
+        resets = torch.zeros(st.num_transitions_per_env, st.num_envs, dtype=torch.uint8, device=st.dones.device)
+        resets[1:] = st.dones[:-1, :, 0]
+        out = []
+        for a, b in st.env_ranges(self.num_mini_batches):
+            wins = [(st.observations[t0:t1, a:b].contiguous(), resets[t0:t1, a:b].contiguous(), st.labels[t0:t1, a:b].flatten(0, 1))
+                    for t0, t1 in st.windows(self.gradient_length)]
+            out.append(((st.h0[a:b].contiguous(), st.c0[a:b].contiguous()), wins))
+        return out
+
+    def _update_recurrent(self):
+        """truncated back-propagation through time: per epoch and env range the state starts at (h0, c0) and is carried from window to
+        window as data -- no gradient, and from the parameters of that moment, as rsl_rl's Distillation carries it --; one optimizer step
+        per (range, window)"""
+        ac, batches = self.actor_critic, self.window_batches()
+        self.num_updates = self.num_learning_epochs * sum(len(wins) for _, wins in batches)
+        ctx = self._blas_for_update() if self._on_device else contextlib.nullcontext()
+        sums = self._sums.zero_() if self._on_device else None
+        total = 0.0
+        with ctx:
+            for _ in range(self.num_learning_epochs):
+                for (h, c), wins in batches:
+                    for obs, resets, labels in wins:
+                        out, h, c = ac.memory_a.sequence_bptt(obs, resets, h, c)
+                        loss = distill_loss(ac.actor(out.flatten(0, 1)), labels, self.loss_type, self._fused)
+                        self.optimizer.zero_grad(set_to_none=False)
+                        if self._on_device:   # (no host round trip inside the loop)
+                            loss.backward()
+                            self._tail_step(loss.detach(), sums)
+                            continue
+                        if not torch.isfinite(loss):
+                            continue
+                        loss.backward()
+                        if not torch.isfinite(nn.utils.clip_grad_norm_(self._params, self.max_grad_norm)):
+                            continue
+                        self.optimizer.step()
+                        total += loss.item()
+        return sums[0].item() / self.num_updates if self._on_device else total / self.num_updates
+
+    def update(self):
+        if self._recurrent:
+            return self._update_recurrent()
+        st = self.storage
+        mb =st.num_envs * st.num_transitions_per_env // self.num_mini_batches
         obs, labels = st.observations.flatten(0, 1), st.labels.flatten(0, 1)
         indices = torch.randperm(self.num_mini_batches * mb, requires_grad=False, device=self.device)   # one permutation, reused by every epoch
         self.num_updates = self.num_learning_epochs * self.num_mini_batches

@@ -15,7 +15,11 @@ front of the actor's MLP and another in front of the critic's; each MLP reads it
 Contiguous fp32 tensors on a HIP device go through libgrx_ppo.so (include/grx_ppo.h grx_lstm_cell / grx_lstm_cell_backward: one launch
 each); `lstm_cell_torch` / `lstm_cell_backward_torch` spell the same two operations in torch for the CPU, and GRX_LSTM_FUSED=0 forces
 them on the device too.  The parameters live in a real nn.LSTM(D, H, 1) named `rnn`, so initialisation and the state-dict keys
-(`memory_a.rnn.weight_ih_l0` ...) are rsl_rl's."""
+(`memory_a.rnn.weight_ih_l0` ...) are rsl_rl's.
+
+LSTMSequenceBPTT is the sequence for the recurrent distillation student's truncated BPTT: the same forward, the last
+state returned as data for the next window, and a backward whose per-step chain is one launch (include/grx_ppo_bptt.h grx_lstm_bptt_step;
+GRX_LSTM_BPTT_FUSED=0: LSTMSequence's three-launch spelling).  PPO's update keeps LSTMSequence."""
 import copy
 import ctypes as C
 import os
@@ -85,6 +89,12 @@ def _lib():
         lib.grx_lstm_cell_preact.argtypes = [C.c_int] * 3 + [fp] * 8 + [C.c_void_p]
         lib.grx_lstm_cell_backward.restype = C.c_int
         lib.grx_lstm_cell_backward.argtypes = [C.c_int] * 2 + [fp] * 7 + [C.c_void_p]
+        lib.grx_lstm_bptt_step.restype = C.c_int
+        lib.grx_lstm_bptt_step.argtypes = [C.c_int] * 2 + [fp] * 10 + [C.c_void_p]
+        lib.grx_lstm_bptt_step_tile.restype = C.c_int
+        lib.grx_lstm_bptt_step_tile.argtypes = [C.c_int] * 3 + [fp] * 10 + [C.c_void_p]
+        lib.grx_lstm_bptt_dh.restype = C.c_int
+        lib.grx_lstm_bptt_dh.argtypes = [C.c_int] * 2 + [fp] * 5 + [C.c_void_p]
         lib._lstm_ready = True
     return lib
 
@@ -124,6 +134,34 @@ def lstm_cell_backward_hip(dh, dc_in, acts, c_prev, reset, dG, dc_prev):
                                            dc_prev.data_ptr(), _stream(dh))
     if rc:
         raise RuntimeError(f"grx_lstm_cell_backward failed ({rc}): M {M}, H {H}")
+
+
+def lstm_bptt_step_hip(dG_next, w_hh, reset_next, dh_out, dc_in, acts, c_prev, reset, dG, dc_prev, tile_units=None):
+    """grx_lstm_bptt_step into dG, dc_prev: one launch for dh = dh_out + dG_next W_hh (zero where reset_next is set) and the cell's
+    element-wise backward on it.  tile_units: the measurement hook grx_lstm_bptt_step_tile (tools/bptt_time.py)"""
+    M, H = dh_out.shape
+    lib = _lib()
+    args = (M, H, _ptr(dG_next), w_hh.data_ptr(), _ptr(reset_next), dh_out.data_ptr(), _ptr(dc_in), acts.data_ptr(), c_prev.data_ptr(), _ptr(reset),
+            dG.data_ptr(), dc_prev.data_ptr(), _stream(dh_out))
+    with torch.cuda.device(dh_out.device):
+        rc = lib.grx_lstm_bptt_step(*args) if tile_units is None else lib.grx_lstm_bptt_step_tile(int(tile_units), *args)
+    if rc:
+        raise RuntimeError(f"grx_lstm_bptt_step failed ({rc}): M {M}, H {H}")
+
+
+def lstm_bptt_dh_hip(dG_next, w_hh, reset_next, dh_out):
+    """grx_lstm_bptt_dh: dh [M, H] = dh_out + dG_next W_hh as grx_lstm_bptt_step's reduction forms it (tests)"""
+    M, H = dh_out.shape
+    dh = torch.empty_like(dh_out)
+    with torch.cuda.device(dh_out.device):
+        rc = _lib().grx_lstm_bptt_dh(M, H, _ptr(dG_next), w_hh.data_ptr(), _ptr(reset_next), dh_out.data_ptr(), dh.data_ptr(), _stream(dh_out))
+    if rc:
+        raise RuntimeError(f"grx_lstm_bptt_dh failed ({rc}): M {M}, H {H}")
+    return dh
+
+
+def _bptt_fused_enabled():
+    return os.environ.get("GRX_LSTM_BPTT_FUSED", "1") != "0"
 
 
 def _use_hip(x):
@@ -196,6 +234,62 @@ class LSTMSequence(torch.autograd.Function):
             db = colsum(dG2)
         else:
             db = dG2.sum(0)
+        return dx, None, None, None, dw_ih, dw_hh, db, db.clone()
+
+
+class LSTMSequenceBPTT(torch.autograd.Function):
+    """LSTMSequence for truncated back-propagation through time (the recurrent distillation student): the same forward,
+    which also returns the last step's (h, c) -- data for the next window, marked non-differentiable --, and a backward whose per-step chain
+    dh_t = dh_out_t + (dG_{t+1} W_hh where step t + 1 was not reset), then the cell's element-wise backward, is ONE launch
+    (grx_lstm_bptt_step) instead of a product, an addcmul and grx_lstm_cell_backward.  GRX_LSTM_BPTT_FUSED=0, GRX_LSTM_FUSED=0 and CPU
+    tensors take LSTMSequence's three-launch spelling, which is the definition.  The products after the loop are LSTMSequence's."""
+
+    @staticmethod
+    def forward(ctx, x, resets, h0, c0, w_ih, w_hh, b_ih, b_hh):
+        T, n, _ = x.shape
+        H = w_hh.shape[1]
+        hip = _use_hip(x)
+        if hip:
+            x, h0, c0, w_ih, w_hh, b_ih, b_hh = (_f32c(t) for t in (x, h0, c0, w_ih, w_hh, b_ih, b_hh))
+            resets = resets.contiguous()
+        hs = x.new_empty(T + 1, n, H)      # hs[t]: the state step t starts from; hs[t + 1]: what it leaves
+        cs = x.new_empty(T + 1, n, H)
+        acts = x.new_empty(T, n, 5 * H)
+        hs[0].copy_(h0); cs[0].copy_(c0)
+        for t in range(T):
+            if hip:
+                lstm_cell_hip(x[t], hs[t], cs[t], resets[t], w_ih, w_hh, b_ih, b_hh, hs[t + 1], cs[t + 1], acts[t])
+            else:
+                h, c, a = lstm_cell_torch(x[t], hs[t], cs[t], resets[t], w_ih, w_hh, b_ih, b_hh)
+                hs[t + 1].copy_(h); cs[t + 1].copy_(c); acts[t].copy_(a)
+        ctx.hip, ctx.fused = hip, hip and _bptt_fused_enabled()
+        ctx.save_for_backward(x, resets, hs, cs, acts, w_ih, w_hh)
+        h_last, c_last = hs[T].clone(), cs[T].clone()
+        ctx.mark_non_differentiable(h_last, c_last)
+        return hs[1:], h_last, c_last
+
+    @staticmethod
+    def backward(ctx, dh_all, _dh_last, _dc_last):
+        if not ctx.fused:
+            return LSTMSequence.backward(ctx, dh_all)
+        x, resets, hs, cs, acts, w_ih, w_hh = ctx.saved_tensors
+        T, n, D = x.shape
+        H = w_hh.shape[1]
+        dh_all = _f32c(dh_all)
+        dG = x.new_empty(T, n, 4 * H)
+        dcs = (x.new_empty(n, H), x.new_empty(n, H))             # the two buffers dc alternates between
+        dc = None
+        for t in reversed(range(T)):
+            nxt, last = dcs[t & 1], t == T - 1
+            lstm_bptt_step_hip(None if last else dG[t + 1], w_hh, None if last else resets[t + 1], dh_all[t], dc, acts[t], cs[t], resets[t], dG[t], nxt)
+            dc = nxt
+        keep = (resets == 0).to(x.dtype).unsqueeze(-1)           # [T, n, 1]
+        dG2 = dG.view(T * n, 4 * H)
+        dx = (dG2 @ w_ih).view(T, n, D) if ctx.needs_input_grad[0] else None
+        dw_ih = dG2.t() @ x.reshape(T * n, D)
+        dw_hh = dG2.t() @ (hs[:-1] * keep).view(T * n, H)       # (the h' a reset row multiplied W_hh with is zero)
+        from .fused_loss import colsum
+        db = colsum(dG2)
         return dx, None, None, None, dw_ih, dw_hh, db, db.clone()
 
 
@@ -290,6 +384,11 @@ class Memory(nn.Module):
         """x [T, n, D], resets [T, n] uint8 (row t: the rows step t takes from zero), (h0, c0) [n, H] -> h [T, n, H], differentiable in
         the LSTM's parameters (and x)"""
         return LSTMSequence.apply(x, resets, h0, c0, *self._weights())
+
+    def sequence_bptt(self, x, resets, h0, c0):
+        """`sequence` for one window of truncated back-propagation through time: (h [T, n, H], h_last, c_last [n, H]); the last state is
+        data for the next window (no gradient), the backward's per-step chain is one launch (LSTMSequenceBPTT)"""
+        return LSTMSequenceBPTT.apply(x, resets, h0, c0, *self._weights())
 
 
 class _TrainLinearOut(torch.autograd.Function):

@@ -77,6 +77,14 @@ class OnPolicyRunner:
         self._alt_inputs = None    # what builds (actor input, critic-slot input) from one step's raw frames in these two modes
         if self.privileged_actor:
             self._check_privileged_actor(env)
+        # a recurrent distillation student: an LSTM in front of the student's MLP, trained by truncated BPTT.  Not config keys
+        # either (`--student_recurrent` / `--rnn_hidden_size` / `--distill_gradient_length` or assignments to train_cfg.runner set them)
+        self.student_recurrent = bool(self.cfg.get("student_recurrent", False))
+        if self.student_recurrent:
+            self._check_student_recurrent()
+        elif self.cfg.get("distill_gradient_length") is not None:
+            raise ValueError("--distill_gradient_length without --student_recurrent: the window of truncated back-propagation through time "
+                             "belongs to a recurrent student (pass --student_recurrent with --distill_from)")
         # a recurrent policy: an LSTM in front of the actor's and the critic's MLP.  Not config keys either (`--recurrent` /
         # `--rnn_hidden_size` or assignments to train_cfg.runner.policy_class_name / train_cfg.policy.rnn_hidden_size set them)
         self.recurrent = bool(getattr(policy_cls, "is_recurrent", False))
@@ -184,14 +192,25 @@ class OnPolicyRunner:
                 self.teacher_obs_normalizer = EmpiricalNormalization(teacher["width"]).to(device)
                 self.teacher_obs_normalizer.load_state_dict(teacher["norm"])
                 self.teacher_obs_normalizer.eval()
-            actor_critic = StudentTeacher(actor_in, teacher["width"], env.num_actions, actor_hidden_dims=self.policy_cfg["actor_hidden_dims"],
-                                          teacher_hidden_dims=teacher["hidden"], activation=self.policy_cfg.get("activation", "elu"),
-                                          noise_std=float(self.cfg.get("distill_noise_std", 0.1))).to(device)
+            student_kw, alg_kw = {}, {}
+            student_cls = StudentTeacher
+            if self.student_recurrent:   # (nothing of it is imported otherwise)
+                from .distillation import StudentTeacherRecurrent as student_cls
+                student_kw = {"rnn_hidden_size": self.student_rnn_hidden_size}
+                alg_kw = {"gradient_length": self.distill_gradient_length}
+            actor_critic = student_cls(actor_in, teacher["width"], env.num_actions, actor_hidden_dims=self.policy_cfg["actor_hidden_dims"],
+                                       teacher_hidden_dims=teacher["hidden"], activation=self.policy_cfg.get("activation", "elu"),
+                                       noise_std=float(self.cfg.get("distill_noise_std", 0.1)), **student_kw).to(device)
             actor_critic.load_teacher(teacher["state"])
             self.algorithm = _ALGORITHMS["Distillation"](actor_critic=actor_critic, device=device, loss_type=self.cfg.get("distill_loss", "mse"),
-                                                         **self.algorithm_cfg)
+                                                         **self.algorithm_cfg, **alg_kw)
             self.distillation = {"teacher_stream": teacher["stream"], "teacher_history": teacher["history"], "teacher_width": teacher["width"],
                                  "loss": self.algorithm.loss_type}
+            if self.student_recurrent:
+                # save() / load() / get_inference_policy() treat the student as the recurrent actor it is: the checkpoint carries
+                # "recurrent", and an ordinary `--recurrent --rnn_hidden_size H` runner loads it (the checks above ran for an MLP policy)
+                self.recurrent = True
+                self.distillation["student"] = {"recurrent": self.student_rnn_hidden_size, "gradient_length": self.distill_gradient_length}
             self._alt_inputs = self._distill_inputs
         else:
             # (with an estimator the policy acts on [x | est(x)]: E more columns; the normaliser's statistics stay actor_in wide)
@@ -796,13 +815,29 @@ class OnPolicyRunner:
         if self.privileged_actor:
             raise ValueError("--recurrent and --privileged_actor exclude each other: a recurrent teacher is not implemented")
         if self.distill_from is not None:
-            raise NotImplementedError("--recurrent with --distill_from: a recurrent student is not implemented (distillation trains an MLP student)")
+            raise NotImplementedError("--recurrent with --distill_from: --recurrent builds PPO's recurrent actor-critic, which distillation does "
+                                      "not train (a recurrent student is --distill_from with --student_recurrent)")
         if self.algorithm_cfg.get("precision", "fp32") != "fp32":
             raise ValueError(f"--recurrent with --precision {self.algorithm_cfg['precision']}: the recurrent policy runs in fp32")
         if bool(self.cfg.get("exact_resume", False)):
             raise NotImplementedError("--recurrent with --exact_resume: the memories' state is not part of train_state_<it>.pt")
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise NotImplementedError("--recurrent with a world size above 1: a recurrent policy trains in one process only")
+
+    def _check_student_recurrent(self):
+        """the refusals of a recurrent distillation student (--student_recurrent); sets student_rnn_hidden_size and distill_gradient_length"""
+        if self.distill_from is None:
+            raise ValueError("--student_recurrent without --distill_from: the recurrent student is distilled from a teacher's checkpoint "
+                             "(PPO's own recurrent policy is --recurrent)")
+        if self.obs_history_length != 1:
+            raise ValueError(f"--student_recurrent with --obs_history {self.obs_history_length}: the memory replaces the stack, the student "
+                             "reads single actor frames (drop one of the two options)")
+        from .recurrent import check_rnn
+        self.student_rnn_hidden_size = check_rnn("lstm", 1, self.cfg.get("student_rnn_hidden_size", 256))
+        L = self.cfg.get("distill_gradient_length", 15)
+        if not isinstance(L, int) or isinstance(L, bool) or L < 0:
+            raise ValueError(f"--distill_gradient_length must be an integer >= 0 (0: the whole rollout in one window), not {L!r}")
+        self.distill_gradient_length = L
 
     def _check_distillation(self, env, device):
         """the refusals of a distillation run; returns what the checkpoint at distill_from says about its actor (distillation.read_teacher)"""
@@ -1148,10 +1183,15 @@ class OnPolicyRunner:
         ac, sd = self.algorithm.actor_critic, loaded["model_state_dict"]
         ac.actor.load_state_dict({k[len("actor."):]: v for k, v in sd.items() if k.startswith("actor.")})
         ac.assign_noise_std(sd["std"])
+        memory = ""
+        if self.recurrent:   # (load()'s "recurrent" check passed: the checkpoint holds a recurrent student of this hidden size)
+            ac.memory_a.rnn.load_state_dict({k[len("memory_a.rnn."):]: v for k, v in sd.items() if k.startswith("memory_a.rnn.")})
+            memory = ", the actor's memory"
         self.algorithm.invalidate_graphs()
         self.current_learning_iteration = loaded["iter"]
-        print(f"{path} is a distilled checkpoint: loaded the student's actor, std and actor-side normaliser / history; the critic is left as it "
-              "is and the optimizer state is skipped")
+        print(f"{path} is a distilled checkpoint: loaded the student's actor{memory}, std and actor-side normaliser / history; the critic "
+              f"{'and its memory are' if self.recurrent else 'is'} left as {'they are' if self.recurrent else 'it is'} and the optimizer state is "
+              "skipped")
         return loaded["infos"]
 
     def _mean_actor(self):

@@ -72,6 +72,11 @@ def get_args(argv=None):
                    help="Path of a PPO checkpoint: distil its actor into a student on the actor's observations (--obs_history) instead of running PPO")
     p.add_argument("--distill_loss", type=str, choices=["mse", "huber"], help="Behaviour loss of --distill_from (default mse)")
     p.add_argument("--distill_noise_std", type=float, help="Fixed action noise of the student's rollout under --distill_from (default 0.1)")
+    p.add_argument("--student_recurrent", action="store_true", default=False,
+                   help="With --distill_from: the student is an LSTM (--rnn_hidden_size) in front of its MLP, trained by truncated BPTT; "
+                        "play the checkpoint with --recurrent --rnn_hidden_size H")
+    p.add_argument("--distill_gradient_length", type=int,
+                   help="Steps per truncated-BPTT window of --student_recurrent (default 15; 0: the whole rollout in one window)")
     p.add_argument("--recurrent", action="store_true", default=False,
                    help="A recurrent policy: an LSTM in front of the actor's and the critic's MLP (saved in the checkpoint; play needs the same flag)")
     p.add_argument("--rnn_hidden_size", type=int, default=256, help="Hidden size of --recurrent's LSTMs: a multiple of 32 in 32..1024")
@@ -215,6 +220,11 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
             cfg_train.runner.distill_loss = args.distill_loss
         if getattr(args, "distill_noise_std", None) is not None:   # (likewise)
             cfg_train.runner.distill_noise_std = float(args.distill_noise_std)
+        if getattr(args, "student_recurrent", False):   # (likewise; --rnn_hidden_size travels with it as with --recurrent)
+            cfg_train.runner.student_recurrent = True
+            cfg_train.runner.student_rnn_hidden_size = int(getattr(args, "rnn_hidden_size", 256))
+        if getattr(args, "distill_gradient_length", None) is not None:   # (likewise; refused by the runner without --student_recurrent)
+            cfg_train.runner.distill_gradient_length = int(args.distill_gradient_length)
         if getattr(args, "symmetry", None) is not None:   # (likewise: the algorithm config has no such keys otherwise)
             cfg_train.algorithm.symmetry = args.symmetry
             cfg_train.algorithm.symmetry_coef = float(getattr(args, "symmetry_coef", 1.0))
